@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: GiB/s of device-resident shmem_double_sum_to_all, nreduce = 32 Mi.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it sets up the
+operands, runs W warm-up steps, times K steps, writes the timed path's outputs
+if --dump-outputs is given, and prints the one JSON line (`correct`,
+`cpu_baseline` and `guard` are null, `extras` empty).  --full adds everything
+else the line can carry, after the timed steps: the correctness guard on what
+was timed, the kernel-clock cross-check and the measured ceiling of the
+roofline, the CPU baseline and its table, and the extras (other algorithms,
+sizes, precisions and API forms).
 
 A "step" is one pass of the hot path over one batch of synthetic input
 (BASELINE.json metric; DESIGN.md "Measurement"):
@@ -22,8 +31,16 @@ A "step" is one pass of the hot path over one batch of synthetic input
 Timing: W untimed warm-up steps, then K steps bracketed by a barrier and a
 device synchronize on both sides; the max over ranks is reported.  The
 kernel's average launch duration comes from HIP events recorded on the stream
-the kernel runs on.  The CPU baseline (rank 0, N = 1 only) times the oracle
+the kernel runs on.  The CPU baseline (--full; rank 0) times the oracle
 restatement of the reference's src/reduce on the host cores.
+
+--dump-outputs DIR: right after the timed steps, rank 0 writes what the timed
+path left in its output array (N = 1: the fold's accumulator, `acc`; N > 1:
+the collective's target, `target`) as DIR/<name>.npy in float64.  An array
+over 64 MB is written as a fixed sample (DUMP_SAMPLE elements at seeded
+indices, the same in every run).  The operands come from seeded generators,
+so the same arguments give the same inputs, and two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -63,6 +80,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--nreduce", type=int, default=32 * 1024 * 1024)
     ap.add_argument("--algo", default="auto", choices=list(shm.ALGOS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's output array after the last timed step as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample if it is over 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the correctness guard, the roofline's "
+                         "cross-checks, the CPU baseline and the extras (the options below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-reps", type=int, default=20,
                     help="warm calls the N = 1 CPU baseline times (the median is reported)")
@@ -1165,6 +1188,41 @@ def measured_ceiling(ptrs, nbytes, stream_ptr, reps=20):
             "GBps": round(total / med.value / 1e3, 1), "launches": reps}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs writes at most this much
+DUMP_SAMPLE = 1 << 20                 # elements written of an array over the limit
+DUMP_SEED = 0xD0D0
+
+
+def dump_indices(n: int):
+    """The elements --dump-outputs writes of an n-element float64 array: all
+    of them (None) if they fit DUMP_LIMIT_BYTES, else DUMP_SAMPLE sorted
+    indices drawn once from a seeded generator (the same for every run and
+    build, whatever the array holds)."""
+    import numpy as np
+    if n * 8 <= DUMP_LIMIT_BYTES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_output(dirname: str, name: str, values, n: int):
+    """Write `values` (a float64 CUDA tensor of n elements: the timed path's
+    output array) or its fixed sample as dirname/name.npy; returns what was
+    written, for the line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_indices(n)
+    if idx is None:
+        out = values.cpu().numpy()
+    else:
+        out = values[torch.from_numpy(idx).to(values.device)].cpu().numpy()
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, out)
+    return {"file": name + ".npy", "dtype": "float64", "elements": int(out.size), "of": n,
+            "sample": None if idx is None else f"numpy default_rng({DUMP_SEED:#x}).integers(0, {n}, "
+                                               f"{DUMP_SAMPLE}), sorted"}
+
+
 def time_region(fn, steps, stream, barrier):
     """Run fn() `steps` times on `stream`; returns (wall_s, event_s)."""
     barrier()
@@ -1295,7 +1353,19 @@ def main():
     torch.cuda.synchronize()
     stage(rank, "timed region")
     wall, ev = time_region(step, a.steps, stream, barrier)
-    stage(rank, "timed region done; checking")
+    stage(rank, "timed region done")
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left in the timed path's output array,
+        # before anything below runs another step on it
+        out_a, out_name = (acc, "acc") if world == 1 else (tgt_a, "target")
+        if isinstance(out_a, int):
+            blk, out_a = out_a, torch.empty_like(src)
+            shm.memcpy(out_a, blk, nbytes)
+        torch.cuda.synchronize()
+        dumped = dump_output(a.dump_outputs, out_name, out_a, n)
+        del out_a
+        stage(rank, f"outputs written to {a.dump_outputs}")
     wall = max_over_ranks(wall)
     ev = max_over_ranks(ev)
     ms_per_step = wall / a.steps * 1e3
@@ -1304,8 +1374,10 @@ def main():
     aggregate = world * value
     guard = None
 
-    # correctness guard on what was timed
-    if world == 1:
+    # correctness guard on what was timed (--full)
+    if not a.full:
+        ok = None
+    elif world == 1:
         # one more step on the very arrays that were timed, from a known acc
         chk = arr(src.clone(), 0)
         torch.cuda.synchronize()
@@ -1373,35 +1445,36 @@ def main():
                     "device_code_sha256": shm.device_code_sha256(), "alg_bytes_per_launch": alg_bytes,
                     "avg_launch_us": round(t_launch * 1e6, 2),
                     "kernel": "fold_kernel<double,SUM,2 inputs>"}
-        # cross-check of avg_launch_us (HIP events over the timed region): K
-        # more launches of the same step, each timed by its own dispatch
-        # events (the library's kernel clock), after the timed region
-        try:
-            torch.cuda.synchronize()
-            shm.kernel_timing(True)
-            for _ in range(a.steps):
-                step()
-            torch.cuda.synchronize()
-            kt, _ = shm.kernel_times()
-            shm.kernel_timing(False)
-            kus = [us for kind, us in kt if kind == "fold"]
-            if kus:
-                roofline["kernel_clock_us"] = {"mean": round(statistics.mean(kus), 2),
-                                               "median": round(statistics.median(kus), 2),
-                                               "min": round(min(kus), 2), "launches": len(kus)}
-        except Exception as e:   # noqa: BLE001 — a cross-check, never the headline
-            roofline["kernel_clock_us"] = f"error: {type(e).__name__}: {e}"
-        # the measured streaming ceiling beside the spec peak:
-        # a read-only stream over the bench's own three 256 MiB arrays
-        try:
-            ptr = lambda x: x if isinstance(x, int) else x.data_ptr()   # noqa: E731
-            mc = measured_ceiling([ptr(acc), ptr(inp), tgt.data_ptr()], nbytes, sp)
-            if mc:
-                roofline["measured_ceiling_GBps"] = mc["GBps"]
-                roofline["frac_of_measured_ceiling"] = round(achieved / mc["GBps"], 4)
-                roofline["measured_ceiling"] = mc
-        except Exception as e:   # noqa: BLE001
-            roofline["measured_ceiling"] = f"error: {type(e).__name__}: {e}"
+        if a.full:
+            # cross-check of avg_launch_us (HIP events over the timed region): K
+            # more launches of the same step, each timed by its own dispatch
+            # events (the library's kernel clock), after the timed region
+            try:
+                torch.cuda.synchronize()
+                shm.kernel_timing(True)
+                for _ in range(a.steps):
+                    step()
+                torch.cuda.synchronize()
+                kt, _ = shm.kernel_times()
+                shm.kernel_timing(False)
+                kus = [us for kind, us in kt if kind == "fold"]
+                if kus:
+                    roofline["kernel_clock_us"] = {"mean": round(statistics.mean(kus), 2),
+                                                   "median": round(statistics.median(kus), 2),
+                                                   "min": round(min(kus), 2), "launches": len(kus)}
+            except Exception as e:   # noqa: BLE001 — a cross-check, never the headline
+                roofline["kernel_clock_us"] = f"error: {type(e).__name__}: {e}"
+            # the measured streaming ceiling beside the spec peak:
+            # a read-only stream over the bench's own three 256 MiB arrays
+            try:
+                ptr = lambda x: x if isinstance(x, int) else x.data_ptr()   # noqa: E731
+                mc = measured_ceiling([ptr(acc), ptr(inp), tgt.data_ptr()], nbytes, sp)
+                if mc:
+                    roofline["measured_ceiling_GBps"] = mc["GBps"]
+                    roofline["frac_of_measured_ceiling"] = round(achieved / mc["GBps"], 4)
+                    roofline["measured_ceiling"] = mc
+            except Exception as e:   # noqa: BLE001
+                roofline["measured_ceiling"] = f"error: {type(e).__name__}: {e}"
     else:
         t_call = ev / a.steps
         xgmi_bytes = 2 * (world - 1) / world * nbytes        # per GPU, RS + AG
@@ -1418,7 +1491,7 @@ def main():
                                   "around the timed steps (max over ranks)"}
 
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not a.no_cpu_baseline:
         # the reference's CPU src/reduce on this host, in the same run
         # (north_star): at N > 1 the line's own config on N PE processes
         stage(rank, "cpu baseline")
@@ -1450,6 +1523,7 @@ def main():
                    "none (one PE: the step is the local fold, no exchange)",
                    "arrays": "symmetric heap (shmem_malloc, HBM)" if use_heap else "hipMalloc (torch)"},
         "roofline": roofline, "cpu_baseline": cpu, "correct": ok, "extras": extras,
+        "full": a.full, "outputs": dumped,
     }
     if world > 1:
         line["aggregate_GiBps"] = round(aggregate, 2)
@@ -1460,7 +1534,7 @@ def main():
             "fields at N > 1 are aggregate (N x nreduce x size / t) unless named algbw")
         line["guard"] = guard
     emitted = threading.Lock()
-    exit_code = 0 if ok else 1
+    exit_code = 1 if ok is False else 0      # a plain run checks nothing: ok is None
 
     def emit(note=None):
         """Print the one JSON line (rank 0), at most once."""
@@ -1504,10 +1578,11 @@ def main():
             # does not first see a peer vanish from a collective and take
             # the extra's error path instead
             time.sleep(2.0)
-        os._exit(0 if ok else 1)
+        os._exit(exit_code)
     timer = threading.Timer(a.extras_timeout, watchdog)
     timer.daemon = True
-    timer.start()
+    if a.full:
+        timer.start()
 
     only = {x for x in a.extras_only.split(",") if x}
 
@@ -1521,7 +1596,9 @@ def main():
         except Exception as e:   # noqa: BLE001 — an extra never costs the headline
             extras[name] = f"error: {type(e).__name__}: {e}"
 
-    if world == 1:
+    if not a.full:
+        pass      # a plain run: the line as it stands
+    elif world == 1:
         if a.extras:
             # the drop-in call itself at PE_size = 1 (copy semantics, reduce-op.c:213-216)
             def api_pe_size_1():
@@ -1670,17 +1747,20 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    # Leave without the interpreter's and the runtimes' exit-time teardown
-    # (RCCL communicator, HIP): the line is out, and nothing the driver
-    # reads depends on it (the node block's /dev/shm name went at init).
-    # Under rocprofv3 (it sets ROCPROF* variables) leave normally instead: its
-    # tool writes the traces and counters at exit.
+    # N = 1 leaves normally (shmem_finalize, then the interpreter's own exit),
+    # so whatever observes the process at exit (exit handlers, library
+    # destructors, a profiler's tool) runs, as for any program that loads the
+    # library.  N > 1 leaves without the interpreter's and the runtimes'
+    # exit-time teardown (RCCL communicator, HIP): the line is out, and
+    # nothing the driver reads depends on it (the node block's /dev/shm name
+    # went at init); except under rocprofv3 (it sets ROCPROF* variables),
+    # whose tool writes the traces and counters at exit.
     sys.stdout.flush()
     sys.stderr.flush()
-    if any(k.startswith("ROCPROF") for k in os.environ):
+    if world == 1 or any(k.startswith("ROCPROF") for k in os.environ):
         shm.finalize()
-        sys.exit(0 if ok else 1)
-    os._exit(0 if ok else 1)
+        sys.exit(exit_code)
+    os._exit(exit_code)
 
 
 if __name__ == "__main__":

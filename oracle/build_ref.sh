@@ -34,6 +34,26 @@ if [ -z "$first" ] || [ -z "$last" ] || [ "$first" -ne 71 ] || [ "$last" -ne 150
 fi
 
 mkdir -p "$HERE/_ref"
+
+# The reference's public headers as gcc precompiled headers (binary, in _ref/
+# like the object above): shmem.h alone, and shmem.h + pshmem.h
+# (oracle/ref_api.h).  tests/test_abi.py compiles against them with
+# -I oracle/_ref, under the same -std=c99 and no -O they are made with, so the
+# test reads nothing outside the tree.
+HDR="$REF/src/shmem.h"
+PHDR="$REF/src/pshmem.h"
+if [ -f "$HDR" ] && [ -f "$PHDR" ]; then
+    G1="$HERE/_ref/shmem.h.gch"
+    G2="$HERE/_ref/ref_api.h.gch"
+    if ! { [ "$G1" -nt "$HDR" ] && [ "$G2" -nt "$HDR" ] && [ "$G2" -nt "$PHDR" ] \
+           && [ "$G2" -nt "$HERE/ref_api.h" ] && [ "$G1" -nt "$0" ] && [ "$G2" -nt "$0" ]; }; then
+        gcc -std=c99 -x c-header "$HDR" -o "$G1.tmp"
+        mv "$G1.tmp" "$G1"
+        gcc -std=c99 -I "$REF/src" -x c-header "$HERE/ref_api.h" -o "$G2.tmp"
+        mv "$G2.tmp" "$G2"
+    fi
+fi
+
 [ "$OUT" -nt "$SRC" ] && [ "$OUT" -nt "$HERE/ref_ops_harness.c" ] && [ "$OUT" -nt "$0" ] && exit 0
 {
     printf '#include <complex.h>\n#line %d "%s"\n' "$first" "$SRC"

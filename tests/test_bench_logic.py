@@ -178,3 +178,29 @@ def test_auto_recommendation_partial_sets_may_name_rccl(bench):
         ["direct", "allreduce", "allreduce", "rccl", "rccl"]
     assert row["8B"]["fastest"] == "signal"
     assert rec["env"]["SHMEMX_AUTO_PARTIAL"] == "0:direct,181:allreduce,1482910:rccl"
+
+
+def test_dump_outputs_sample_is_fixed_and_small(bench, tmp_path):
+    """--dump-outputs: an array within 64 MB is written whole, a larger one
+    as the same seeded sample in every run (sorted indices inside the array);
+    the file is float64 and holds exactly the sampled elements."""
+    import numpy as np
+    import torch
+    assert bench.dump_indices(bench.DUMP_LIMIT_BYTES // 8) is None
+    n = 32 * 1024 * 1024                       # the headline's array: 256 MiB
+    idx = bench.dump_indices(n)
+    assert idx.size == bench.DUMP_SAMPLE and idx.size * 8 <= bench.DUMP_LIMIT_BYTES
+    assert idx.min() >= 0 and idx.max() < n and (np.diff(idx) >= 0).all()
+    assert np.array_equal(idx, bench.dump_indices(n))
+    small = torch.arange(1000, dtype=torch.float64) * 0.5
+    info = bench.dump_output(str(tmp_path / "out"), "acc", small, 1000)
+    got = np.load(tmp_path / "out" / "acc.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy())
+    assert info["elements"] == 1000 and info["sample"] is None
+    m = bench.DUMP_LIMIT_BYTES // 8 + 1        # one element over the limit: sampled
+    big = torch.arange(m, dtype=torch.float64)
+    info = bench.dump_output(str(tmp_path / "out"), "target", big, m)
+    got = np.load(tmp_path / "out" / "target.npy")
+    assert got.dtype == np.float64 and got.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(got, bench.dump_indices(m).astype(np.float64))
+    assert info["elements"] == bench.DUMP_SAMPLE and info["of"] == m

@@ -1,5 +1,5 @@
 """bench.py's N > 1 path, run the way the driver runs it
-(`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`),
+(`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --full`),
 with every rank on the box's one GPU: on the default RCCL transport through
 the RCCL test double (tests/native/fake_rccl.cpp), and on the IPC transport.
 
@@ -60,7 +60,7 @@ def test_bench_multi_rank_line(tmp_path, transport, npes):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={npes}",
            "--master-addr", "127.0.0.1", f"--master-port={free_port()}",
            os.path.join(REPO, "bench.py"), "--gpus", str(npes), "--steps", "3", "--warmup", "1",
-           "--nreduce", str(1 << 20), "--extras-max-nreduce", str(1 << 20), "--extras-timeout", "240"]
+           "--full", "--nreduce", str(1 << 20), "--extras-max-nreduce", str(1 << 20), "--extras-timeout", "240"]
     logdir = os.environ.get("GPU_TEST_LOGDIR")
     err_path = (os.path.join(logdir, f"bench_multi_{transport}_{npes}.err") if logdir
                 else str(tmp_path / "bench.err"))
@@ -166,7 +166,7 @@ def test_bench_multi_watchdog_cut_keeps_line(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", f"--master-port={free_port()}",
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--nreduce", str(1 << 20), "--extras-max-nreduce", str(1 << 20),
+           "--full", "--nreduce", str(1 << 20), "--extras-max-nreduce", str(1 << 20),
            "--extras-only", "algo_crossover", "--extras-timeout", "1.5"]
     err_path = str(tmp_path / "bench.err")
     with open(err_path, "w") as err:
@@ -197,7 +197,7 @@ def test_bench_multi_guard_catches_a_corrupt_element(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", f"--master-port={free_port()}",
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--nreduce", str(1 << 20), "--extras", "0", "--no-cpu-baseline", "--corrupt-guard-test"]
+           "--full", "--nreduce", str(1 << 20), "--extras", "0", "--no-cpu-baseline", "--corrupt-guard-test"]
     err_path = str(tmp_path / "bench.err")
     with open(err_path, "w") as err:
         p = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=err, text=True,

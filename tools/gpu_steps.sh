@@ -6,9 +6,9 @@
 #   smoke          __graft_entry__.smoke()
 #   tests          pytest -m gpu (the whole GPU suite; PE logs in gpurun_out/ipclogs)
 #   tests_k        the GPU tests matching $TESTS_K (pytest -k)
-#   bench          the driver's default command, python bench.py (N = 1)
+#   bench          the whole N = 1 line, python bench.py --full (guard, CPU baseline, extras)
 #   bench2         the same again (run-to-run check of value and cpu_baseline)
-#   trace          rocprofv3 --kernel-trace --stats of the driver's command, python3 bench.py
+#   trace          rocprofv3 --kernel-trace --stats of the same command, python3 bench.py --full
 #   pmc            FETCH_SIZE and WRITE_SIZE of the headline, one rocprofv3 pass each, then
 #                  tools/summarize_prof.py -> gpurun_out/profiles/$TAG_{kernel_stats.csv,pmc.json}
 #   pmc_kernels    every shipped kernel (tools/pmc_kernels.py): trace + FETCH/WRITE passes
@@ -44,7 +44,7 @@ json_line() {   # json_line <log> <json>: the bench line alone, as a JSON file
     grep '^{"metric"' "$1" > "$2" && cut -c1-400 "$2"
 }
 
-BENCH_HEAD="python3 bench.py --steps 20 --warmup 5 --extras 0 --no-cpu-baseline"
+BENCH_HEAD="python3 bench.py --steps 20 --warmup 5"   # a plain run: the headline alone
 TAG=${TAG:-r06}
 
 for step in "$@"; do
@@ -60,9 +60,9 @@ for step in "$@"; do
         tail -3 $O/gpu_tests_k.log ;;
     bench|bench2)   # the log keeps rank 0's progress lines; the .json holds the one bench line
         b=bench_n1; [ $step = bench2 ] && b=bench_n1_b
-        run 600 $O/$b.log python3 bench.py; json_line $O/$b.log $O/$b.json ;;
+        run 600 $O/$b.log python3 bench.py --full; json_line $O/$b.log $O/$b.json ;;
     trace)
-        run 600 $O/trace.log rocprofv3 --kernel-trace --stats -d $O/trace -o trace --output-format csv -- python3 bench.py
+        run 600 $O/trace.log rocprofv3 --kernel-trace --stats -d $O/trace -o trace --output-format csv -- python3 bench.py --full
         grep '"metric"' $O/trace.log | cut -c1-300
         python3 tools/trace_by_grid.py $O/trace fold > $O/trace_by_grid.txt; cat $O/trace_by_grid.txt ;;
     pmc)
@@ -121,13 +121,13 @@ for step in "$@"; do
         q=4; [ "$np" -gt 4 ] && q=2     # 8 processes' queues on one GPU (tests/test_gpu_ipc.py)
         GPU_MAX_HW_QUEUES=$q SHMEMX_TRANSPORT=ipc SHMEMX_SHARE_GPU=1 run 900 $O/rehearse_ipc_n$np.log python3 -m torch.distributed.run \
             --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus $np \
-            --steps 10 --warmup 3
+            --steps 10 --warmup 3 --full
         json_line $O/rehearse_ipc_n$np.log $O/rehearse_ipc_n$np.json ;;
     rehearse_rccl)   # $REH_N ranks (default 2)
         np=${REH_N:-2}; q=4; [ "$np" -gt 4 ] && q=2
         GPU_MAX_HW_QUEUES=$q FAKE_RCCL=$PWD/tests/native/libfake_rccl.so SHMEMX_SHARE_GPU=1 run 900 $O/rehearse_rccl_n$np.log \
             python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 \
-            --master-port 29512 bench.py --gpus $np --steps 10 --warmup 3 --extras-max-nreduce ${REH_EXTRAS_MAX:-1048576}
+            --master-port 29512 bench.py --gpus $np --steps 10 --warmup 3 --full --extras-max-nreduce ${REH_EXTRAS_MAX:-1048576}
         json_line $O/rehearse_rccl_n$np.log $O/rehearse_rccl_n$np.json ;;
     *) echo "unknown step $step"; exit 2 ;;
     esac
