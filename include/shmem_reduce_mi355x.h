@@ -305,9 +305,15 @@ int shmemx_fold_n_peers_on_stream(int type, int op, void *out,
                                   void *stream);
 
 /* DIRECT's all-gather step as one launch: nseg (<= 16) byte ranges
- * srcs[i] -> dsts[i] copied concurrently (blockIdx.y = segment), so reads
- * from every peer's HBM are in flight at once.  Device (or IPC-mapped peer)
- * pointers, stream-ordered; ranges must not overlap. */
+ * srcs[i] -> dsts[i] copied concurrently (consecutive runs of up to 256
+ * workgroups take the segments in turn, each workgroup 32 KiB of its
+ * segment), so reads from every peer's HBM are in flight at once.  Any byte
+ * alignment: 16-byte vectors where a segment's source and target agree mod
+ * 16, bytes where they do not.  Zero-length segments are skipped (their
+ * pointers may be NULL).  Device (or IPC-mapped peer) pointers,
+ * stream-ordered; ranges must not overlap.  EINVAL, before anything is
+ * launched, for nseg outside 0..16 or a segment whose source and target
+ * are distinct and overlap. */
 int shmemx_gather_on_stream(const void *const *srcs, void *const *dsts,
                             const size_t *bytes, int nseg, void *stream);
 
@@ -476,7 +482,11 @@ int shmemx_op_on_device(int type, int op);
 /* Position-aware 64-bit checksum of nelems elements (host or device memory;
  * long double: value bytes only) — XOR over 8-byte words w_j of
  * splitmix64-finalise(w_j + (j+1) * 0x9E3779B97F4A7C15); computed by a gfx950
- * kernel (wave shuffle + LDS partials).  shmemx_verify: collective over the
+ * kernel (wave shuffle + LDS partials).  The pointer needs only the
+ * element's own alignment: host memory is staged into a device workspace, and
+ * device memory that is not 16-byte aligned (a heap block at +8, a slice) is
+ * first copied there too, on the library's stream; 16-byte aligned device
+ * memory is read in place.  shmemx_verify: collective over the
  * active set, *all_equal = 1 iff every member's target has the same checksum
  * (what the A2A and RCCL algorithms guarantee after a reduction). */
 int shmemx_checksum(int type, const void *ptr, size_t nelems, unsigned long long *out);

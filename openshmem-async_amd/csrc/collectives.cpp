@@ -295,6 +295,16 @@ int checksum_impl(int type, const void *ptr, size_t nelems, unsigned long long *
     if (bytes) ptr = heap::device_operand(ptr, bytes);   // mirrored heap: the HBM twin
     DevBuf in = device_in(ptr, bytes, g_state.cws_src, g_state.cws_src_bytes, s);
     if (bytes && !in.dev) return set_error(SHMEMX_ENOMEM);
+    // The kernel reads 16-byte vectors from the array's first byte (the words
+    // are defined from there, so it peels no head): device memory at any
+    // other alignment (a heap block at +8, a slice of an array) is copied to
+    // the workspace first, on the same stream, and that copy is hashed.
+    if (bytes && (reinterpret_cast<uintptr_t>(in.dev) & 15u) != 0) {
+        char *ws = static_cast<char *>(grow(g_state.cws_src, g_state.cws_src_bytes, bytes));
+        if (!ws) return set_error(SHMEMX_ENOMEM);
+        SHMX_HIP(hipMemcpyAsync(ws, in.dev, bytes, hipMemcpyDeviceToDevice, s));
+        in.dev = ws;
+    }
     // The kernel stores the result straight into page-locked host memory,
     // then this call's epoch behind it: the host polls the epoch instead of
     // waiting for the stream (no copy command, no completion signal to wake

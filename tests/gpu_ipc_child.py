@@ -417,6 +417,12 @@ elif scenario == "signal":
         for n in (1013, 70001):
             seed += 1
             run_case(t, op, n, (0, 0, npes), "signal", "heapoff", seed)
+            # that target (block + 3 elements: 6, 8 or 12 mod 16 but for the
+            # 16-byte types) by shmemx_verify: the checksum of device memory
+            # off 16-B alignment, equal on every member
+            if not shm.verify(t, HEAP_TGT + 3 * oracle.NP_DTYPE[t]().itemsize, n, 0, 0, npes) \
+                    or shm.last_error():
+                fails.append(f"verify {t} n={n} of the heapoff target: err={shm.last_error()}")
     for n in (0, 1, 2, 63, 65, 1 << 20):
         seed += 1
         run_case("double", "sum", n, (0, 0, npes), "signal", "heap", seed)

@@ -299,6 +299,98 @@ def test_copy_moves_bits_every_size_offset_and_nt_path(cuda, shm, t):
             assert bool((dst[:off] == 0xA5).all()) and bool((dst[off + n * sz:] == 0xA5).all()), (t, n, off)
 
 
+def _dev_bytes(torch, a, lead=0):
+    """a's bytes on the device behind `lead` bytes of padding (torch buffers
+    are at least 16-byte aligned, so `lead` is the data's address mod 16)."""
+    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    buf = torch.zeros(lead + raw.size, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    buf[lead:] = torch.from_numpy(raw.copy()).cuda()
+    return buf
+
+
+def _fold_into_guarded(torch, shm, t, op, ins, n, isz, lead, peers, dtype):
+    """fold_n of `ins` (device addresses) into a canary-filled byte buffer at
+    byte offset 32 + lead; returns the n result elements after checking that
+    every byte around them still holds the canary."""
+    lo = 32 + lead
+    outbuf = torch.full((lo + n * isz + 48,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert outbuf.data_ptr() % 16 == 0
+    shm.fold_n(t, op, outbuf.data_ptr() + lo, ins, n, peers=peers)
+    torch.cuda.synchronize()
+    got = outbuf.cpu().numpy()
+    assert (got[:lo] == 0xA5).all() and (got[lo + n * isz:] == 0xA5).all(), "wrote outside"
+    return got[lo:lo + n * isz].view(dtype)
+
+
+# (fold_n route, inputs, types, 16-byte vectors per workgroup chunk): the
+# two-input fold, the runtime-nins kernel, its software-pipelined long double
+# branch (nins >= 3), and the peers kernels for up to 4, 8 and 16 inputs (the
+# complex product, a heavy op, takes the runtime kernel there too).
+_LIGHT = (("short", "max"), ("double", "sum"), ("complexf", "prod"))
+CHUNK_VARIANTS = [
+    pytest.param(False, 2, _LIGHT, 1024, id="fold2"),
+    pytest.param(False, 3, _LIGHT, 1024, id="fold_n3"),
+    pytest.param(False, 3, (("longdouble", "sum"),), 1024, id="fold_n3-longdouble"),
+    pytest.param(True, 3, _LIGHT, 1024, id="peers3"),
+    pytest.param(True, 7, _LIGHT, 1024, id="peers7"),
+    pytest.param(True, 12, _LIGHT, 512, id="peers12"),
+]
+
+
+@pytest.mark.parametrize("peers,P,pairs,C", CHUNK_VARIANTS)
+def test_fold_chunk_edges(cuda, shm, oracle, peers, P, pairs, C):
+    """Every fold kernel takes whole chunks of C vectors unguarded and the last
+    partial chunk guarded (base + kBlock * UNROLL <= nvec).  Vector bodies of
+    C - 1, C, C + 1, 2C and 2C + 1 vectors, each with and without a one-element
+    scalar head and tail (16-byte types have neither), bit for bit against
+    the oracle, the bytes around the target untouched.  The fold is
+    element-wise, so the oracle's result over the longest arrays, sliced,
+    is the reference of every case."""
+    import torch
+    for t, op in pairs:
+        isz = shm.type_size(t)
+        E = 16 // isz
+        nmax = (E - 1) + 1 + (2 * C + 1) * E + 1
+        srcs = oracle.sources(t, 1, P, nmax, base_seed=0xC0DE0000 + 131 * P + C)
+        want = oracle.reduce_sim(t, op, srcs, 0, 0, P)[0]
+        dev = [_dev_bytes(torch, srcs[p]) for p in range(P)]
+        for nvec in (C - 1, C, C + 1, 2 * C, 2 * C + 1):
+            for head in ((0, 1) if E > 1 else (0,)):
+                for tail in ((0, 1) if E > 1 else (0,)):
+                    off = E - 1 if head else 0          # elements: all arrays alike
+                    n = head + nvec * E + tail
+                    ins = [d.data_ptr() + off * isz for d in dev]
+                    got = _fold_into_guarded(torch, shm, t, op, ins, n, isz, off * isz % 16,
+                                             peers, srcs.dtype)
+                    assert same_bits(got, want[off:off + n]), (t, op, P, nvec, head, tail)
+
+
+@pytest.mark.parametrize("op", ["sum", "prod"])
+def test_fold_complexd_at_8_mod_16(cuda, shm, oracle, op):
+    """double _Complex has 8-byte alignment in C: an array at an address that
+    is 8 mod 16 is legal, and is what an 8-byte-aligned allocator hands out.
+    dispatch() sends it down the all-scalar path with 16-byte loads and stores
+    at 8-byte aligned addresses.  The copy, the two-input fold, the runtime
+    kernel and the peers route with every array at 8 mod 16, and the runtime
+    kernel with only the target there.  (long double's C alignment is 16: no
+    such array exists.)"""
+    import torch
+    t, nmax = "complexd", 5003
+    srcs = oracle.sources(t, 1, 3, nmax, base_seed=0x8D160000)
+    at8 = [_dev_bytes(torch, srcs[p], 8) for p in range(3)]
+    at0 = [_dev_bytes(torch, srcs[p], 0) for p in range(3)]
+    for P, peers, src_lead in ((1, False, 8), (2, False, 8), (3, False, 8), (3, True, 8),
+                               (3, False, 0)):
+        want = oracle.reduce_sim(t, op, srcs[:P], 0, 0, P)[0]
+        bufs = at8 if src_lead else at0
+        ins = [b.data_ptr() + src_lead for b in bufs[:P]]
+        assert all(p % 16 == src_lead for p in ins)
+        for n in (1, 255, 256, 257, 5003):
+            got = _fold_into_guarded(torch, shm, t, op, ins, n, 16, 8, peers, srcs.dtype)
+            assert same_bits(got, want[:n]), (op, P, peers, src_lead, n)
+
+
 def test_kernel_clock_times_fold_and_copy(cuda, shm):
     """shmemx_kernel_timing / shmemx_kernel_times: every fold-family launch
     while on is timed by its own dispatch events, in launch order, with its
