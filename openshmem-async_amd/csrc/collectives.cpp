@@ -43,10 +43,10 @@ namespace shmx {
 
 namespace {
 
-struct SetInfo {
-    int P = 0, m = -1, step = 1, start = 0;
-    bool world = false;
-    int peer(int i) const { return start + i * step; }
+// The caller's active set and its index in it.
+struct SetInfo : ActiveSet {
+    int m = -1;
+    bool world() const { return ActiveSet::world(g_state.npes); }
 };
 
 // Validate (PE_start, logPE_stride, PE_size) and the caller's membership.
@@ -55,18 +55,14 @@ int set_info(int start, int logstride, int size, SetInfo &si) {
     if (start < 0 || logstride < 0 || logstride > 30 || size < 1) return set_error(SHMEMX_EINVAL);
     if ((long long)start + (long long)(size - 1) * (1LL << logstride) >= g_state.npes)
         return set_error(SHMEMX_EINVAL);
-    si.P = size;
-    si.start = start;
-    si.step = 1 << logstride;
-    si.world = start == 0 && (logstride == 0 || size == 1) && size == g_state.npes;
+    static_cast<ActiveSet &>(si) = ActiveSet::of(start, logstride, size);
     if (!is_member(g_state.pe, start, logstride, size, &si.m)) return set_error(SHMEMX_ENOTMEMBER);
     if ((size > 1 || g_state.force_collective) && !g_state.comm && !node::up())
         return set_error(SHMEMX_ENOINIT);
     return SHMEMX_OK;
 }
 
-bool collective(const SetInfo &si) { return si.P > 1 || g_state.force_collective; }
-
+bool collective(const SetInfo &si) { return si.size > 1 || g_state.force_collective; }
 
 // A device view of a possibly host-resident buffer.
 struct DevBuf {
@@ -126,25 +122,25 @@ int barrier_impl(int start, int logstride, int size) {
     // (system-scope fence on every XCD) visible to the peers, whose stores
     // through shmemx_heap_ptr this GPU will then not see through stale lines
     const bool coll = collective(si);
-    if (coll && si.P > 1) fence_and_wait(s);
+    if (coll && si.size > 1) fence_and_wait(s);
     else SHMX_HIP(hipStreamSynchronize(s));
     trace(LOG_BARRIER, "set (%d,%d,%d) member %d", start, logstride, size, si.m);
     if (!coll) return SHMEMX_OK;
     if (!g_state.comm) {   // IPC transport
-        node::barrier(si.start, si.step, si.P);
+        node::barrier(si.start, si.step, si.size);
         return SHMEMX_OK;
     }
-    char *tok = token_area(si.P);
+    char *tok = token_area(si.size);
     if (!tok) return set_error(SHMEMX_ENOMEM);
-    if (si.world) {
+    if (si.world()) {
         SHMX_NCCL(ncclAllReduce(tok, tok, 1, ncclUint8, ncclMax, g_state.comm, s));
     } else {
         // every member hears from every other member (one byte each way)
         SHMX_NCCL(ncclGroupStart());
-        for (int i = 0; i < si.P; ++i) {
+        for (int i = 0; i < si.size; ++i) {
             if (i == si.m) continue;
-            SHMX_NCCL(ncclSend(tok, 1, ncclUint8, si.peer(i), g_state.comm, s));
-            SHMX_NCCL(ncclRecv(tok + 64 + i, 1, ncclUint8, si.peer(i), g_state.comm, s));
+            SHMX_NCCL(ncclSend(tok, 1, ncclUint8, si.pe_of(i), g_state.comm, s));
+            SHMX_NCCL(ncclRecv(tok + 64 + i, 1, ncclUint8, si.pe_of(i), g_state.comm, s));
         }
         SHMX_NCCL(ncclGroupEnd());
     }
@@ -173,9 +169,9 @@ int broadcast_impl(size_t esize, void *target, const void *source, size_t nelems
     if (si.m != root_idx) target = tw.ptr();
     if (!g_state.comm) {   // IPC transport
         return ipc_broadcast(static_cast<char *>(target), static_cast<const char *>(source),
-                             bytes, root_idx, si.start, si.step, si.P, si.m, s);
+                             bytes, root_idx, si.start, si.step, si.size, si.m, s);
     }
-    const int root = si.peer(root_idx);
+    const int root = si.pe_of(root_idx);
     const bool is_root = si.m == root_idx;
     DevBuf in, out;
     if (is_root) {
@@ -185,15 +181,15 @@ int broadcast_impl(size_t esize, void *target, const void *source, size_t nelems
         out = device_out(target, bytes, g_state.cws_tgt, g_state.cws_tgt_bytes);
         if (!out.dev) return set_error(SHMEMX_ENOMEM);
     }
-    if (si.world) {
+    if (si.world()) {
         // in place on the root (sendbuff == recvbuff): its target is untouched
         char *buf = is_root ? in.dev : out.dev;
         SHMX_NCCL(ncclBroadcast(buf, buf, bytes, ncclUint8, root, g_state.comm, s));
     } else {
         SHMX_NCCL(ncclGroupStart());
         if (is_root) {
-            for (int i = 0; i < si.P; ++i)
-                if (i != si.m) SHMX_NCCL(ncclSend(in.dev, bytes, ncclUint8, si.peer(i), g_state.comm, s));
+            for (int i = 0; i < si.size; ++i)
+                if (i != si.m) SHMX_NCCL(ncclSend(in.dev, bytes, ncclUint8, si.pe_of(i), g_state.comm, s));
         } else {
             SHMX_NCCL(ncclRecv(out.dev, bytes, ncclUint8, root, g_state.comm, s));
         }
@@ -222,39 +218,39 @@ int collect_impl(size_t esize, void *target, const void *source, size_t nelems, 
         if (nelems && !source) return set_error(SHMEMX_EINVAL);
         size_t total = 0;
         const int rc = ipc_collect(static_cast<char *>(target), static_cast<const char *>(source), esize,
-                                   nelems, si.start, si.step, si.P, si.m, &total, s);
+                                   nelems, si.start, si.step, si.size, si.m, &total, s);
         if (rc == SHMEMX_OK && target) heap::device_wrote(user_target, total, s);
         trace(LOG_COLLECT, "%s over IPC: %zu bytes mine, %zu in all, set (%d,%d,%d)",
               fixed ? "fcollect" : "collect", nelems * esize, total, start, logstride, size);
         return rc;
     }
-    std::vector<long long> counts(si.P, (long long)nelems);
+    std::vector<long long> counts(si.size, (long long)nelems);
     if (!fixed && collective(si)) {
         // every member's count (the reference passes it down a chain of
         // shmem_long_p, collect-linear.c:83-110)
         long long *cnt = static_cast<long long *>(grow(g_state.token, g_state.token_bytes,
-                                                       sizeof(long long) * (si.P + 8)));
+                                                       sizeof(long long) * (si.size + 8)));
         if (!cnt) return set_error(SHMEMX_ENOMEM);
         const long long mine = (long long)nelems;
         SHMX_HIP(hipMemcpyAsync(cnt + si.m, &mine, sizeof mine, hipMemcpyHostToDevice, s));
-        if (si.world) {
+        if (si.world()) {
             SHMX_NCCL(ncclAllGather(cnt + si.m, cnt, 1, ncclInt64, g_state.comm, s));
         } else {
             SHMX_NCCL(ncclGroupStart());
-            for (int i = 0; i < si.P; ++i) {
+            for (int i = 0; i < si.size; ++i) {
                 if (i == si.m) continue;
-                SHMX_NCCL(ncclSend(cnt + si.m, 1, ncclInt64, si.peer(i), g_state.comm, s));
-                SHMX_NCCL(ncclRecv(cnt + i, 1, ncclInt64, si.peer(i), g_state.comm, s));
+                SHMX_NCCL(ncclSend(cnt + si.m, 1, ncclInt64, si.pe_of(i), g_state.comm, s));
+                SHMX_NCCL(ncclRecv(cnt + i, 1, ncclInt64, si.pe_of(i), g_state.comm, s));
             }
             SHMX_NCCL(ncclGroupEnd());
         }
-        SHMX_HIP(hipMemcpyAsync(counts.data(), cnt, sizeof(long long) * si.P,
+        SHMX_HIP(hipMemcpyAsync(counts.data(), cnt, sizeof(long long) * si.size,
                                 hipMemcpyDeviceToHost, s));
         SHMX_HIP(hipStreamSynchronize(s));
     }
-    std::vector<size_t> off(si.P + 1, 0);
-    for (int i = 0; i < si.P; ++i) off[i + 1] = off[i] + (size_t)counts[i] * esize;
-    const size_t mine = (size_t)counts[si.m] * esize, total = off[si.P];
+    std::vector<size_t> off(si.size + 1, 0);
+    for (int i = 0; i < si.size; ++i) off[i + 1] = off[i] + (size_t)counts[i] * esize;
+    const size_t mine = (size_t)counts[si.m] * esize, total = off[si.size];
     trace(LOG_COLLECT, "%s: %zu of %zu bytes at offset %zu, set (%d,%d,%d)",
           fixed ? "fcollect" : "collect", mine, total, off[si.m], start, logstride, size);
     if (!total) return SHMEMX_OK;
@@ -265,15 +261,15 @@ int collect_impl(size_t esize, void *target, const void *source, size_t nelems, 
     if (mine && in.dev != out.dev + off[si.m])
         SHMX_HIP(hipMemcpyAsync(out.dev + off[si.m], in.dev, mine, hipMemcpyDeviceToDevice, s));
     if (collective(si)) {
-        if (si.world && fixed && !g_state.force_collective) {
+        if (si.world() && fixed && !g_state.force_collective) {
             SHMX_NCCL(ncclAllGather(out.dev + off[si.m], out.dev, mine, ncclUint8, g_state.comm, s));
         } else {
             SHMX_NCCL(ncclGroupStart());
-            for (int i = 0; i < si.P; ++i) {
+            for (int i = 0; i < si.size; ++i) {
                 if (i == si.m) continue;
                 const size_t bi = off[i + 1] - off[i];
-                if (mine) SHMX_NCCL(ncclSend(out.dev + off[si.m], mine, ncclUint8, si.peer(i), g_state.comm, s));
-                if (bi) SHMX_NCCL(ncclRecv(out.dev + off[i], bi, ncclUint8, si.peer(i), g_state.comm, s));
+                if (mine) SHMX_NCCL(ncclSend(out.dev + off[si.m], mine, ncclUint8, si.pe_of(i), g_state.comm, s));
+                if (bi) SHMX_NCCL(ncclRecv(out.dev + off[i], bi, ncclUint8, si.pe_of(i), g_state.comm, s));
             }
             SHMX_NCCL(ncclGroupEnd());
         }
@@ -340,7 +336,7 @@ int exchange_u64(int start, int logstride, int size, unsigned long long mine,
                  std::vector<unsigned long long> &all) {
     SetInfo si;
     if (int rc = set_info(start, logstride, size, si)) return rc;
-    all.assign(si.P, mine);
+    all.assign(si.size, mine);
     if (collective(si) && (!g_state.comm || node::up())) {
         // the values travel in the node block's descriptors (host only: two
         // host barriers, where an RCCL all-gather costs a stream round trip);
@@ -348,29 +344,28 @@ int exchange_u64(int start, int logstride, int size, unsigned long long mine,
         node::Desc d;
         d.aux = mine;
         node::put_desc(d);
-        node::barrier(si.start, si.step, si.P);
-        for (int i = 0; i < si.P; ++i) all[i] = node::get_desc(si.peer(i)).aux;
-        node::barrier(si.start, si.step, si.P);   // all read before any descriptor changes
+        node::barrier(si.start, si.step, si.size);
+        for (int i = 0; i < si.size; ++i) all[i] = node::get_desc(si.pe_of(i)).aux;
+        node::barrier(si.start, si.step, si.size);   // all read before any descriptor changes
     } else if (collective(si)) {
         hipStream_t s = g_state.stream;
-        g_state.lib_stream_dirty = true;
-    g_state.lib_stream_dirty = true;   // until someone sees it drained (service.hip)
+        g_state.lib_stream_dirty = true;   // until someone sees it drained (service.hip)
         unsigned long long *d = static_cast<unsigned long long *>(
-            grow(g_state.token, g_state.token_bytes, sizeof(unsigned long long) * (si.P + 8)));
+            grow(g_state.token, g_state.token_bytes, sizeof(unsigned long long) * (si.size + 8)));
         if (!d) return set_error(SHMEMX_ENOMEM);
         SHMX_HIP(hipMemcpyAsync(d + si.m, &mine, sizeof mine, hipMemcpyHostToDevice, s));
-        if (si.world) {
+        if (si.world()) {
             SHMX_NCCL(ncclAllGather(d + si.m, d, 1, ncclUint64, g_state.comm, s));
         } else {
             SHMX_NCCL(ncclGroupStart());
-            for (int i = 0; i < si.P; ++i) {
+            for (int i = 0; i < si.size; ++i) {
                 if (i == si.m) continue;
-                SHMX_NCCL(ncclSend(d + si.m, 1, ncclUint64, si.peer(i), g_state.comm, s));
-                SHMX_NCCL(ncclRecv(d + i, 1, ncclUint64, si.peer(i), g_state.comm, s));
+                SHMX_NCCL(ncclSend(d + si.m, 1, ncclUint64, si.pe_of(i), g_state.comm, s));
+                SHMX_NCCL(ncclRecv(d + i, 1, ncclUint64, si.pe_of(i), g_state.comm, s));
             }
             SHMX_NCCL(ncclGroupEnd());
         }
-        SHMX_HIP(hipMemcpyAsync(all.data(), d, sizeof(unsigned long long) * si.P,
+        SHMX_HIP(hipMemcpyAsync(all.data(), d, sizeof(unsigned long long) * si.size,
                                 hipMemcpyDeviceToHost, s));
         SHMX_HIP(hipStreamSynchronize(s));
     }

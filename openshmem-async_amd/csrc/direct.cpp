@@ -52,6 +52,7 @@
 #include "heap.h"
 #include "internal.h"
 #include "node.h"
+#include "set_geom.h"
 #include "shmem_reduce_mi355x.h"
 #include "state.h"
 
@@ -60,17 +61,7 @@ namespace shmx {
 namespace {
 
 constexpr size_t kDefaultScratchBytes = size_t(512) << 20;
-constexpr size_t kDefaultOneShotBytes = size_t(256) << 10;
 constexpr size_t kDefaultFusedTwoShotBytes = size_t(4) << 20;
-
-// Arrays up to this size take the one-shot path ($SHMEMX_DIRECT_ONESHOT_KB).
-size_t oneshot_bytes() {
-    static const size_t b = [] {
-        const char *e = std::getenv("SHMEMX_DIRECT_ONESHOT_KB");
-        return e ? size_t(std::atol(e)) << 10 : kDefaultOneShotBytes;
-    }();
-    return b;
-}
 
 struct Scratch {
     char *base = nullptr;
@@ -100,15 +91,14 @@ std::unordered_set<uint64_t> g_voted;
 
 // The region of each member that DIRECT reads: its source, and its target
 // when the peers gather from it.
-bool map_members(const std::vector<node::Desc> &desc, bool local_write, int start, int step,
-                 int P) {
+bool map_members(const std::vector<node::Desc> &desc, bool local_write, const ActiveSet &set) {
     std::vector<std::pair<node::Region, int>> regs;
-    for (int i = 0; i < P; ++i) {
-        regs.emplace_back(static_cast<node::Region>(desc[i].src.region), start + i * step);
+    for (int i = 0; i < set.size; ++i) {
+        regs.emplace_back(static_cast<node::Region>(desc[i].src.region), set.pe_of(i));
         if (!local_write)
-            regs.emplace_back(static_cast<node::Region>(desc[i].tgt.region), start + i * step);
+            regs.emplace_back(static_cast<node::Region>(desc[i].tgt.region), set.pe_of(i));
     }
-    return map_regions(regs, start, step, P);
+    return map_regions(regs, set);
 }
 
 }  // namespace
@@ -136,12 +126,12 @@ double now_us() {
 // of them alike; the combinations that passed are remembered, and every
 // member decides identically whether to vote (same set, same regions, same
 // generations from the shared block).
-bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, int start, int step, int P) {
+bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set) {
     uint64_t key = 1469598103934665603ull;
     auto mix = [&key](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
-    mix((uint64_t)start);
-    mix((uint64_t)step);
-    mix((uint64_t)P);
+    mix((uint64_t)set.start);
+    mix((uint64_t)set.step);
+    mix((uint64_t)set.size);
     bool ok = true;
     for (const auto &rp : regs) {
         mix((uint64_t)rp.first);
@@ -153,7 +143,7 @@ bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, int star
         if (!ok) fatal("peer region mapped before is gone", node::last_ipc_error());
         return true;
     }
-    if (!node::agree(start, step, P, ok)) return false;
+    if (!node::agree(set.start, set.step, set.size, ok)) return false;
     g_voted.insert(key);
     return true;
 }
@@ -287,6 +277,14 @@ long twoshot_kb_from_env() {
 long g_fused_twoshot_kb = twoshot_kb_from_env();
 }  // namespace
 
+size_t oneshot_bytes() {
+    static const size_t b = [] {
+        const char *e = std::getenv("SHMEMX_DIRECT_ONESHOT_KB");
+        return e ? size_t(std::atol(e)) << 10 : kDefaultOneShotBytes;
+    }();
+    return b;
+}
+
 size_t fused_twoshot_bytes() { return size_t(g_fused_twoshot_kb) << 10; }
 
 long set_fused_twoshot_kb(long kb) {
@@ -295,8 +293,9 @@ long set_fused_twoshot_kb(long kb) {
     return prev;
 }
 
-bool signal_args(int start, int step, int P, SignalArgs *sa) {
+bool signal_args(const ActiveSet &set, SignalArgs *sa) {
     unsigned long long *mine = heap::signal_area();
+    const int P = set.size;
     if (!mine || P > kMaxFoldInputs) return false;
     *sa = SignalArgs{};
     sa->mine = mine;
@@ -310,7 +309,7 @@ bool signal_args(int start, int step, int P, SignalArgs *sa) {
     sa->fence_stats = fr.stats;
     const uint64_t sig = heap::signal_offset();
     for (int i = 0; i < P; ++i) {
-        const int q = start + i * step;
+        const int q = set.pe_of(i);
         char *b = node::peer_base(node::kHeap, q);
         if (!b) return false;
         sa->pe[i] = q;
@@ -373,31 +372,28 @@ namespace {
 // DIRECT's one shot as one fused launch (launch_signal_fold): every member's
 // source (heap or staged scratch, per the descriptors) and every member's
 // heap segment (the signal counters) mapped, then the launch and one wait.
-int direct_fused(int type, int op, char *tgt, size_t n, int start, int step, int P, int m,
+int direct_fused(int type, int op, char *tgt, size_t n, const ActiveSet &set, int m,
                  bool own_order, const std::vector<node::Desc> &desc, bool stage_tgt, hipStream_t s) {
+    const int P = set.size;
     std::vector<std::pair<node::Region, int>> regs;
     for (int i = 0; i < P; ++i) {
-        regs.emplace_back(static_cast<node::Region>(desc[i].src.region), start + i * step);
-        regs.emplace_back(node::kHeap, start + i * step);
+        regs.emplace_back(static_cast<node::Region>(desc[i].src.region), set.pe_of(i));
+        regs.emplace_back(node::kHeap, set.pe_of(i));
     }
-    if (!map_regions(regs, start, step, P)) {
+    if (!map_regions(regs, set)) {
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer region (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
     SignalFoldArgs fa{};
-    if (!signal_args(start, step, P, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
+    if (!signal_args(set, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
     fa.gsync = fence_records().gsync;
     const size_t sz = type_size(type);
     char *const scratch_tgt = g_scratch.base + g_scratch.bytes / 2;
     fa.out = stage_tgt ? scratch_tgt : tgt;
     // set order, or mine (src_me first, then the others ascending)
-    auto src_of = [&](int i) {
-        return node::peer_base(static_cast<node::Region>(desc[i].src.region), start + i * step) + desc[i].src.off;
-    };
-    int k = 0;
-    if (own_order) fa.ins[k++] = src_of(m);
-    for (int i = 0; i < P; ++i)
-        if (!own_order || i != m) fa.ins[k++] = src_of(i);
+    fold_inputs(fa.ins, P, m, own_order, [&](int i) {
+        return node::peer_base(static_cast<node::Region>(desc[i].src.region), set.pe_of(i)) + desc[i].src.off;
+    });
     fa.nins = P;
     fa.n = n;
     // The host spins on a page-locked word instead of waiting for the
@@ -417,11 +413,7 @@ int direct_fused(int type, int op, char *tgt, size_t n, int start, int step, int
     wait_host_signal(sig, s);
     g_phase_us[kFold] += now_us() - t0;
     count_fused_call();
-    switch (signal_error()) {
-    case 0: break;
-    case 2: fatal("DIRECT reduction", "a system fence before a device barrier missed an XCD");
-    default: fatal("DIRECT reduction", "a member never reached the device barrier");
-    }
+    check_signal_error("DIRECT reduction");
     return SHMEMX_OK;
 }
 
@@ -429,36 +421,28 @@ int direct_fused(int type, int op, char *tgt, size_t n, int start, int step, int
 // member's source and target in its heap segment, one chunk.  Slice fold,
 // device handshake, gather of the peers' slices, device handshake, in the
 // same kernel; then one wait.
-int direct_fused2(int type, int op, char *tgt, size_t n, int start, int step, int P, int m,
+int direct_fused2(int type, int op, char *tgt, size_t n, const ActiveSet &set, int m,
                   const std::vector<node::Desc> &desc, hipStream_t s) {
+    const int P = set.size;
     std::vector<std::pair<node::Region, int>> regs;
-    for (int i = 0; i < P; ++i) regs.emplace_back(node::kHeap, start + i * step);
-    if (!map_regions(regs, start, step, P)) {
+    for (int i = 0; i < P; ++i) regs.emplace_back(node::kHeap, set.pe_of(i));
+    if (!map_regions(regs, set)) {
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer heap (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
     SignalFoldArgs fa{};
-    if (!signal_args(start, step, P, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
+    if (!signal_args(set, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
     fa.gsync = fence_records().gsync;
-    const size_t sz = type_size(type);
-    const size_t g = sz >= 16 ? 1 : 16 / sz;
-    size_t slice = (n + P - 1) / P;
-    slice = (slice + g - 1) / g * g;
-    auto lo_of = [&](int i) { return std::min(n, (size_t)i * slice); };
-    auto hi_of = [&](int i) { return std::min(n, (size_t)(i + 1) * slice); };
+    const Slices sl(n, P, type_size(type));
     fa.out = tgt;
-    for (int i = 0; i < P; ++i) fa.ins[i] = node::peer_base(node::kHeap, start + i * step) + desc[i].src.off;
+    for (int i = 0; i < P; ++i) fa.ins[i] = node::peer_base(node::kHeap, set.pe_of(i)) + desc[i].src.off;
     fa.nins = P;
     fa.n = n;
     fa.two_shot = 1;
-    fa.lo = lo_of(m);
-    fa.hi = hi_of(m);
-    for (int i = 0; i < P; ++i) {
-        if (i == m || hi_of(i) <= lo_of(i)) continue;
-        fa.gsrc[fa.nseg] = node::peer_base(node::kHeap, start + i * step) + desc[i].tgt.off + lo_of(i) * sz;
-        fa.gdst[fa.nseg] = tgt + lo_of(i) * sz;
-        fa.glen[fa.nseg++] = (hi_of(i) - lo_of(i)) * sz;
-    }
+    fa.lo = sl.lo(m);
+    fa.hi = sl.hi(m);
+    auto tgt_of = [&](int i) { return node::peer_base(node::kHeap, set.pe_of(i)) + desc[i].tgt.off; };
+    fa.nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa.gsrc, fa.gdst, fa.glen);
     const double t0 = now_us();
     SHMX_HIP(launch_signal_fold(type, op, fa, s));   // reduce-op.c:217-250
     const HostSignal sig = next_host_signal();       // a marker: the host spins, no stream wait
@@ -466,11 +450,7 @@ int direct_fused2(int type, int op, char *tgt, size_t n, int start, int step, in
     wait_host_signal(sig, s);
     g_phase_us[kFold] += now_us() - t0;
     count_fused_twoshot_call();
-    switch (signal_error()) {
-    case 0: break;
-    case 2: fatal("DIRECT reduction", "a system fence before a device barrier missed an XCD");
-    default: fatal("DIRECT reduction", "a member never reached the device barrier");
-    }
+    check_signal_error("DIRECT reduction");
     return SHMEMX_OK;
 }
 
@@ -479,6 +459,7 @@ int direct_fused2(int type, int op, char *tgt, size_t n, int start, int step, in
 int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s) {
     const int P = p.nmembers, m = p.member, step = 1 << logstride;
+    const ActiveSet set{start, step, P};
     if (!node::up()) return set_error(SHMEMX_ENOTSUP);
     if (stream_capturing(s)) return set_error(SHMEMX_ENOTSUP);   // host barriers inside
     if (!own_order && P > kMaxFoldInputs) return set_error(SHMEMX_ENOTSUP);   // one gather launch
@@ -486,10 +467,9 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     const size_t sz = (size_t)p.elem_size;
     const size_t n = (size_t)nreduce;
     const size_t bytes = n * sz;
-    const size_t g = sz >= 16 ? 1 : 16 / sz;
+    const size_t g = granule(sz);
     const size_t half = g_scratch.bytes / 2;
     const size_t cmax = std::max(g, (half / sz) / g * g);   // elements per staged chunk
-    auto pe_of = [&](int i) { return start + i * step; };
     // Small arrays: one shot — every member folds the whole array itself (in
     // set order, so all agree, or each in its own) and writes only its own
     // target: one kernel and two barriers instead of two kernels and three.
@@ -543,7 +523,7 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     g_calls += 1;
     std::vector<node::Desc> desc(P);
     auto read_descs = [&] {
-        for (int i = 0; i < P; ++i) desc[i] = i == m ? d : node::get_desc(pe_of(i));
+        for (int i = 0; i < P; ++i) desc[i] = i == m ? d : node::get_desc(set.pe_of(i));
     };
     {
         // The descriptors first, with no fence, on every call whatever its
@@ -577,8 +557,8 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
             bool fuse = true;
             for (int i = 0; i < P; ++i) fuse &= (desc[i].count & bit) != 0;
             if (fuse && one_shot)
-                return direct_fused(type, op, tgt, n, start, step, P, m, own_order, desc, stage_tgt, s);
-            if (fuse) return direct_fused2(type, op, tgt, n, start, step, P, m, desc, s);
+                return direct_fused(type, op, tgt, n, set, m, own_order, desc, stage_tgt, s);
+            if (fuse) return direct_fused2(type, op, tgt, n, set, m, desc, s);
         }
         // my source (and its staging) is complete; reduce-op.c:217
         node_sync(start, step, P, s, &g_phase_us[kEntryWait], &g_phase_us[kEntryBarrier]);
@@ -591,16 +571,16 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         chunked |= (desc[i].count & 1) != 0;
         backwards |= (desc[i].count & 2) != 0;
     }
-    if (!map_members(desc, local_write, start, step, P)) {
+    if (!map_members(desc, local_write, set)) {
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer region (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
     std::vector<char *> sbase(P), tbase(P);
     for (int i = 0; i < P; ++i) {
-        sbase[i] = node::peer_base(static_cast<node::Region>(desc[i].src.region), pe_of(i)) +
+        sbase[i] = node::peer_base(static_cast<node::Region>(desc[i].src.region), set.pe_of(i)) +
                    desc[i].src.off;
         if (!local_write)
-            tbase[i] = node::peer_base(static_cast<node::Region>(desc[i].tgt.region), pe_of(i)) +
+            tbase[i] = node::peer_base(static_cast<node::Region>(desc[i].tgt.region), set.pe_of(i)) +
                        desc[i].tgt.off;
     }
     const size_t C = chunked ? cmax : std::max<size_t>(n, 1);
@@ -625,10 +605,7 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         if (local_write) {
             // own order: src_me first, then the others ascending
             // (reduce-op.c:219-248); one shot: set order
-            int k2 = 0;
-            if (own_order) ins[k2++] = at(sbase[m], desc[m].src, c0);
-            for (int i = 0; i < P; ++i)
-                if (!own_order || i != m) ins[k2++] = at(sbase[i], desc[i].src, c0);
+            fold_inputs(ins.data(), P, m, own_order, [&](int i) { return at(sbase[i], desc[i].src, c0); });
             char *out = stage_tgt ? scratch_tgt : tgt + c0 * sz;
             const double tf = now_us();
             fold_chain(type, op, out, ins.data(), P, cnt, s, true);
@@ -639,11 +616,8 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
             continue;
         }
         // two shots: slice i of the chunk belongs to member i
-        size_t slice = (cnt + P - 1) / P;
-        slice = (slice + g - 1) / g * g;
-        auto lo_of = [&](int i) { return std::min(cnt, (size_t)i * slice); };
-        auto hi_of = [&](int i) { return std::min(cnt, (size_t)(i + 1) * slice); };
-        const size_t lo = lo_of(m), hi = hi_of(m);
+        const Slices sl(cnt, P, sz);
+        const size_t lo = sl.lo(m), hi = sl.hi(m);
         // 1. my slice from every member's source, into my published target
         const double tf = now_us();
         if (hi > lo) {
@@ -654,22 +628,14 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         // every member's slice is final
         node_sync(start, step, P, s, &g_phase_us[kFold], &g_phase_us[kFoldBarrier], tf);
         // 2. every other member's slice (and mine, if it was staged) into my target
-        std::vector<const void *> from;
-        std::vector<void *> to;
-        std::vector<size_t> len;
-        // from member m + 1 on, wrapping (m itself last, when staged): the
-        // gather kernel gives its first blocks to its first segment, so the
-        // members start on different peers' slices
-        for (int r = 1; r <= P; ++r) {
-            const int i = (m + r) % P;
-            if (i == m && !stage_tgt) continue;
-            if (hi_of(i) <= lo_of(i)) continue;
-            from.push_back(at(tbase[i], desc[i].tgt, c0 + lo_of(i)));
-            to.push_back(tgt + (c0 + lo_of(i)) * sz);
-            len.push_back((hi_of(i) - lo_of(i)) * sz);
-        }
+        // from member m + 1 on, wrapping (m itself last, when staged)
+        const void *from[kMaxFoldInputs];
+        void *to[kMaxFoldInputs];
+        size_t len[kMaxFoldInputs];
+        auto tgt_of = [&](int i) { return at(tbase[i], desc[i].tgt, c0); };
+        const int nseg = gather_segments(sl, m, true, stage_tgt, tgt_of, tgt + c0 * sz, from, to, len);
         const double tg = now_us();
-        SHMX_HIP(launch_gather(from.data(), to.data(), len.data(), (int)from.size(), s));
+        SHMX_HIP(launch_gather(from, to, len, nseg, s));
         // reduce-op.c:250: no member reads my slice any more
         node_done(start, step, P, s, &g_phase_us[kGather], &g_phase_us[kExitBarrier], tg);
     }

@@ -73,7 +73,7 @@ int ipc_broadcast(char *target, const char *source, size_t bytes, int root_idx, 
     const bool single = bytes <= half;
     if (root && staged && single) SHMX_HIP(hipMemcpyAsync(scr, source, bytes, hipMemcpyDefault, s));
     node_sync(start, step, P, s);
-    const int root_pe = start + root_idx * step;
+    const int root_pe = ActiveSet{start, step, P}.pe_of(root_idx);
     const node::Desc rd = root ? d : node::get_desc(root_pe);
     const bool chunked = rd.count != 0;
     char *rbase = root ? nullptr : mapped(rd.src, root_pe);
@@ -121,12 +121,13 @@ int ipc_collect(char *target, const char *source, size_t esize, size_t nelems, i
     if (prestaged) SHMX_HIP(hipMemcpyAsync(scr, source, mine, hipMemcpyDefault, s));
     node_sync(start, step, P, s);
 
+    const ActiveSet set{start, step, P};
     std::vector<node::Desc> desc(P);
     std::vector<size_t> len(P), offs(P + 1, 0);
     bool any_staged = false, late_stage = false;
     size_t most = 0;
     for (int i = 0; i < P; ++i) {
-        desc[i] = i == m ? d : node::get_desc(start + i * step);
+        desc[i] = i == m ? d : node::get_desc(set.pe_of(i));
         len[i] = (size_t)desc[i].count * esize;
         offs[i + 1] = offs[i] + len[i];
         if (desc[i].aux) {
@@ -139,7 +140,7 @@ int ipc_collect(char *target, const char *source, size_t esize, size_t nelems, i
     *total_out = total;
     std::vector<char *> base(P, nullptr);
     for (int i = 0; i < P; ++i)
-        if (len[i]) base[i] = mapped(desc[i].src, start + i * step);
+        if (len[i]) base[i] = mapped(desc[i].src, set.pe_of(i));
     bool tstaged = false;
     char *dst = device_target(target, total, &tstaged);
     if (total && !dst) fatal("IPC collect", "no device staging buffer");

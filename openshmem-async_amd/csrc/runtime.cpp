@@ -37,6 +37,7 @@
 #include "internal.h"
 #include "mirror.h"
 #include "node.h"
+#include "set_geom.h"
 #include "shmem_reduce_mi355x.h"
 #include "state.h"
 
@@ -487,16 +488,6 @@ static std::vector<AutoCut> parse_auto_table(const char *var) {
     return cuts;
 }
 
-// Set while reduce_device plans a call being captured into a hipGraph:
-// the table's DIRECT (host barriers, refused under capture) then falls back
-// to the built-in rule, so captured calls still plan.  Every PE of a set
-// must capture its calls alike (as for every stream-ordered collective).
-static thread_local bool t_planning_capture = false;
-// Set while reduce_device plans a call on a partial set that is being
-// captured: a set whose RCCL communicator does not exist yet cannot take an
-// RCCL algorithm (creating one is not a stream operation).
-static thread_local bool t_capturing = false;
-
 // The table's algorithm for an array of `bytes` per PE, or AUTO.
 static int auto_table_algo(bool world, long long bytes) {
     static const std::vector<AutoCut> full = parse_auto_table("SHMEMX_AUTO_FULL");
@@ -508,8 +499,8 @@ static int auto_table_algo(bool world, long long bytes) {
     return algo;
 }
 
-int make_plan(int type, int op, int nreduce, int start, int logstride,
-                     int size, int pe, int npes, int algo, shmemx_plan_t *p) {
+int make_plan(int type, int op, int nreduce, int start, int logstride, int size, int pe, int npes,
+              int algo, shmemx_plan_t *p, PlanCapture cap) {
     std::memset(p, 0, sizeof *p);
     p->member = -1;
     if (!op_valid(type, op)) return SHMEMX_EINVAL;
@@ -524,19 +515,19 @@ int make_plan(int type, int op, int nreduce, int start, int logstride,
     const long long n = nreduce;
     const int P = size;
     const int sz = (int)type_size(type);
-    const long long g = sz >= 16 ? 1 : 16 / sz;  // elements per 16-byte granule
-    const bool world = start == 0 && (logstride == 0 || size == 1) && size == npes;
+    const long long g = (long long)granule(sz);
+    const bool world = ActiveSet::of(start, logstride, size).world(npes);
     // RCCL's own collectives serve the whole job on the world communicator
     // and a partial set on the set's members-only communicator (set_comm.cpp)
     const bool set_rccl = world || (set_comms_enabled() && !set_comm_refused(start, logstride, size) &&
-                                    (!t_capturing || set_comm_cached(start, logstride, size)));
+                                    (!cap.no_new_comm || set_comm_cached(start, logstride, size)));
     const bool rccl_ok = set_rccl && rccl_native(type, op) && !g_state.ipc_only;
     // each member's own fold order (own_order_pair): GATHER's exchange, or
     // DIRECT / SIGNAL reading every member's whole source
     const bool own = P > 1 && own_order_pair(type, op);
     if (algo == SHMEMX_ALGO_AUTO && P > 1) {
         const int t = auto_table_algo(world, n * sz);
-        const bool pull_ok = g_state.node_shared && P <= kMaxFoldInputs && !t_planning_capture;
+        const bool pull_ok = g_state.node_shared && P <= kMaxFoldInputs && !cap.auto_algo;
         if (((t == SHMEMX_ALGO_RCCL || t == SHMEMX_ALGO_ALLREDUCE) && rccl_ok) ||
             (t == SHMEMX_ALGO_A2A && !g_state.ipc_only && !own) || (t == SHMEMX_ALGO_DIRECT && pull_ok) ||
             t == SHMEMX_ALGO_GATHER)
@@ -576,7 +567,7 @@ int make_plan(int type, int op, int nreduce, int start, int logstride,
         return SHMEMX_OK;
     }
     switch (algo) {
-    case SHMEMX_ALGO_RCCL:
+    case SHMEMX_ALGO_RCCL:   // equal shards of whole granules for the reduce-scatter, the rest a tail
         p->chunk = (n / (P * g)) * g;
         p->main = p->chunk * P;
         p->tail = n - p->main;
@@ -585,19 +576,14 @@ int make_plan(int type, int op, int nreduce, int start, int logstride,
         p->chunk = n;
         p->main = n;
         break;
-    case SHMEMX_ALGO_A2A: {
-        long long c = (n + P - 1) / P;
-        c = (c + g - 1) / g * g;
-        p->chunk = c;
-        p->ws_bytes = c * P * sz;
+    case SHMEMX_ALGO_A2A:
+        p->chunk = (long long)Slices(n, P, sz).slice;
+        p->ws_bytes = p->chunk * P * sz;
         break;
-    }
     case SHMEMX_ALGO_DIRECT:
-    case SHMEMX_ALGO_SIGNAL: {   // slice per member (own order: all of it); no workspace
-        const long long c = (n + P - 1) / P;
-        p->chunk = own ? n : (c + g - 1) / g * g;
+    case SHMEMX_ALGO_SIGNAL:   // slice per member (own order: all of it); no workspace
+        p->chunk = own ? n : (long long)Slices(n, P, sz).slice;
         break;
-    }
     default:  // GATHER (IPC transport: read in place, no workspace)
         p->chunk = n;
         p->ws_bytes = g_state.ipc_only ? 0 : n * P * sz;
@@ -666,25 +652,27 @@ void trace_reference_overlap(const void *target, const void *source, size_t byte
           target, source, (long)bytes);
 }
 
-static long long count_of(long long n, long long chunk, int i) {
-    const long long lo = chunk * i;
-    return std::max(0LL, std::min(chunk, n - lo));
-}
-
-void fold_chain(int type, int op, void *out, const void **ins, int nins, size_t n,
-                hipStream_t s, bool peers) {
-    // Left fold in groups of kMaxFoldInputs: out = fold(ins[0..15]);
-    // out = fold(out, ins[16..30]); ... (same order as one long fold).
+// Left fold in groups of kMaxFoldInputs: out = fold(ins[0..15]);
+// out = fold(out, ins[16..30]); ... (same order as one long fold).  The first
+// launch error ends it.
+static hipError_t fold_groups(int type, int op, void *out, const void *const *ins, int nins, size_t n,
+                              hipStream_t s, bool peers) {
     auto fold = peers ? launch_fold_peers : launch_fold;
     int done = std::min(nins, kMaxFoldInputs);
-    SHMX_HIP(fold(type, op, out, ins, done, n, s));
-    while (done < nins) {
+    hipError_t e = fold(type, op, out, ins, done, n, s);
+    while (e == hipSuccess && done < nins) {
         const void *grp[kMaxFoldInputs];
         grp[0] = out;
         int k = 1;
         while (k < kMaxFoldInputs && done < nins) grp[k++] = ins[done++];
-        SHMX_HIP(fold(type, op, out, grp, k, n, s));
+        e = fold(type, op, out, grp, k, n, s);
     }
+    return e;
+}
+
+void fold_chain(int type, int op, void *out, const void **ins, int nins, size_t n,
+                hipStream_t s, bool peers) {
+    SHMX_HIP(fold_groups(type, op, out, ins, nins, n, s, peers));
 }
 
 static int reduce_exchange(int type, int op, char *tgt, const char *src, int nreduce,
@@ -696,20 +684,17 @@ int reduce_device(int type, int op, void *target, const void *source,
                          int nreduce, int start, int logstride, int size,
                          int algo, hipStream_t s) {
     shmemx_plan_t p;
-    const bool partial = !(start == 0 && (logstride == 0 || size == 1) && size == g_state.npes);
+    const bool partial = !ActiveSet::of(start, logstride, size).world(g_state.npes);
     const bool capturing = (algo == SHMEMX_ALGO_AUTO || partial) && stream_capturing(s);
-    t_planning_capture = algo == SHMEMX_ALGO_AUTO && capturing;
-    t_capturing = capturing;
+    const PlanCapture cap{algo == SHMEMX_ALGO_AUTO && capturing, capturing};
     int rc = make_plan(type, op, nreduce, start, logstride, size, g_state.pe,
-                       g_state.npes, algo, &p);
+                       g_state.npes, algo, &p, cap);
     // a partial set's first RCCL call: its members agree on and make its
     // communicator; if they refuse (a member's cache is full), all of them
     // plan again without it (A2A under auto, ENOTSUP for an explicit rccl)
     if (!rc && partial && size > 1 && (p.algo == SHMEMX_ALGO_RCCL || p.algo == SHMEMX_ALGO_ALLREDUCE) &&
         !set_comm_cached(start, logstride, size) && !set_comm_prepare(start, logstride, size, p.member, s))
-        rc = make_plan(type, op, nreduce, start, logstride, size, g_state.pe, g_state.npes, algo, &p);
-    t_planning_capture = false;
-    t_capturing = false;
+        rc = make_plan(type, op, nreduce, start, logstride, size, g_state.pe, g_state.npes, algo, &p, cap);
     if (rc) return set_error(rc);
     if (nreduce == 0) return SHMEMX_OK;
     const bool collective = size > 1 || g_state.force_collective;
@@ -721,9 +706,7 @@ int reduce_device(int type, int op, void *target, const void *source,
         return signal_reduce(type, op, static_cast<char *>(target), static_cast<const char *>(source),
                              nreduce, start, logstride, p, own, s);
     }
-    const bool over_ipc = p.algo == SHMEMX_ALGO_DIRECT ||
-                          (p.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only);
-    if (collective && over_ipc) {
+    if (collective && pulls_over_ipc(p)) {
         const bool own_order = p.algo == SHMEMX_ALGO_GATHER || own;
         if (log_enabled(LOG_REDUCTION))
             trace(LOG_REDUCTION, "type %d op %d nreduce %d set (%d,%d,%d) member %d algo %s%s",
@@ -769,7 +752,7 @@ static int reduce_exchange(int type, int op, char *tgt, const char *src, int nre
     const size_t sz = (size_t)p.elem_size;
     const size_t bytes = sz * (size_t)nreduce;
 
-    const int P = size, m = p.member, step = 1 << logstride;
+    const int P = size, m = p.member;
     if (P == 1 && !g_state.force_collective) {  // reduce-op.c:213-216, no peers: a copy
         if (tgt != src) {
             const void *in[1] = {src};
@@ -777,12 +760,12 @@ static int reduce_exchange(int type, int op, char *tgt, const char *src, int nre
         }
         return SHMEMX_OK;
     }
-    auto peer = [&](int i) { return start + i * step; };
+    const ActiveSet set = ActiveSet::of(start, logstride, P);
+    const bool world = set.world(g_state.npes);
 
     if (p.algo == SHMEMX_ALGO_ALLREDUCE || p.algo == SHMEMX_ALGO_RCCL) {
         // the whole job: the world communicator; a partial set: its own
         // members-only communicator, rank = index in the set
-        const bool world = start == 0 && (step == 1 || P == 1) && P == g_state.npes;
         ncclComm_t comm = world ? g_state.comm : set_comm(start, logstride, P, m, s);
         ncclDataType_t dt;
         rccl_dtype(type, &dt);
@@ -811,25 +794,25 @@ static int reduce_exchange(int type, int op, char *tgt, const char *src, int nre
 
     if (p.algo == SHMEMX_ALGO_A2A) {
         const size_t cb = (size_t)p.chunk * sz;
-        const long long my_cnt = count_of(n, p.chunk, m);
+        const Slices sl(n, P, sz);   // make_plan's: sl.slice == p.chunk
+        const size_t my_cnt = sl.count(m);
         // 1. shard exchange: member i gets chunk i of every source
         SHMX_NCCL(ncclGroupStart());
         for (int i = 0; i < P; ++i) {
             if (i == m) continue;
-            const long long ci = count_of(n, p.chunk, i);
-            if (ci > 0) SHMX_NCCL(ncclSend(src + i * cb, (size_t)ci * sz, ncclUint8, peer(i), g_state.comm, s));
-            if (my_cnt > 0) SHMX_NCCL(ncclRecv(ws + i * cb, (size_t)my_cnt * sz, ncclUint8, peer(i), g_state.comm, s));
+            const size_t ci = sl.count(i);
+            if (ci > 0) SHMX_NCCL(ncclSend(src + i * cb, ci * sz, ncclUint8, set.pe_of(i), g_state.comm, s));
+            if (my_cnt > 0) SHMX_NCCL(ncclRecv(ws + i * cb, my_cnt * sz, ncclUint8, set.pe_of(i), g_state.comm, s));
         }
         SHMX_NCCL(ncclGroupEnd());
         // 2. fold the P copies of my chunk in active-set order (PE_start first)
         if (my_cnt > 0) {
             std::vector<const void *> ins(P);
             for (int i = 0; i < P; ++i) ins[i] = (i == m) ? src + m * cb : ws + i * cb;
-            fold_chain(type, op, tgt + m * cb, ins.data(), P, (size_t)my_cnt, s);
+            fold_chain(type, op, tgt + m * cb, ins.data(), P, my_cnt, s);
         }
         // 3. shard all-gather: RCCL's own all-gather (in place) when the set
         // is the whole job and every shard is full, grouped p2p otherwise
-        const bool world = start == 0 && step == 1 && P == g_state.npes;
         if (world && n == (long long)P * p.chunk) {
             SHMX_NCCL(ncclAllGather(tgt + m * cb, tgt, cb, ncclUint8, g_state.comm, s));
             return SHMEMX_OK;
@@ -837,9 +820,9 @@ static int reduce_exchange(int type, int op, char *tgt, const char *src, int nre
         SHMX_NCCL(ncclGroupStart());
         for (int i = 0; i < P; ++i) {
             if (i == m) continue;
-            const long long ci = count_of(n, p.chunk, i);
-            if (my_cnt > 0) SHMX_NCCL(ncclSend(tgt + m * cb, (size_t)my_cnt * sz, ncclUint8, peer(i), g_state.comm, s));
-            if (ci > 0) SHMX_NCCL(ncclRecv(tgt + i * cb, (size_t)ci * sz, ncclUint8, peer(i), g_state.comm, s));
+            const size_t ci = sl.count(i);
+            if (my_cnt > 0) SHMX_NCCL(ncclSend(tgt + m * cb, my_cnt * sz, ncclUint8, set.pe_of(i), g_state.comm, s));
+            if (ci > 0) SHMX_NCCL(ncclRecv(tgt + i * cb, ci * sz, ncclUint8, set.pe_of(i), g_state.comm, s));
         }
         SHMX_NCCL(ncclGroupEnd());
         return SHMEMX_OK;
@@ -848,25 +831,20 @@ static int reduce_exchange(int type, int op, char *tgt, const char *src, int nre
     // GATHER: every source to every member (RCCL's all-gather on the whole
     // job, grouped p2p on a partial set), then the reference's own order on
     // each PE: r = src_me; r = op(r, src_p) for p ascending, p != me.
-    if (start == 0 && step == 1 && P == g_state.npes) {
+    if (world) {
         SHMX_NCCL(ncclAllGather(src, ws, bytes, ncclUint8, g_state.comm, s));
     } else {
         SHMX_NCCL(ncclGroupStart());
         for (int i = 0; i < P; ++i) {
             if (i == m) continue;
-            SHMX_NCCL(ncclSend(src, bytes, ncclUint8, peer(i), g_state.comm, s));
-            SHMX_NCCL(ncclRecv(ws + (size_t)i * bytes, bytes, ncclUint8, peer(i), g_state.comm, s));
+            SHMX_NCCL(ncclSend(src, bytes, ncclUint8, set.pe_of(i), g_state.comm, s));
+            SHMX_NCCL(ncclRecv(ws + (size_t)i * bytes, bytes, ncclUint8, set.pe_of(i), g_state.comm, s));
         }
         SHMX_NCCL(ncclGroupEnd());
     }
-    {
-        std::vector<const void *> ins;
-        ins.reserve(P);
-        ins.push_back(src);
-        for (int i = 0; i < P; ++i)
-            if (i != m) ins.push_back(ws + (size_t)i * bytes);
-        fold_chain(type, op, tgt, ins.data(), P, (size_t)nreduce, s);
-    }
+    std::vector<const void *> ins(P);
+    fold_inputs(ins.data(), P, m, true, [&](int i) { return i == m ? src : ws + (size_t)i * bytes; });
+    fold_chain(type, op, tgt, ins.data(), P, (size_t)nreduce, s);
     return SHMEMX_OK;
 }
 
@@ -1186,7 +1164,6 @@ int shmemx_fold_on_stream(int type, int op, void *acc, const void *in,
 
 static int fold_n(int type, int op, void *out, const void *const *ins, int nins, size_t nelems,
                   void *stream, bool peers) {
-    auto launch = peers ? launch_fold_peers : launch_fold;
     t_last_error = SHMEMX_OK;
     const LocalDevice dev(stream);
     if (!op_on_device(type, op)) return set_error(op_valid(type, op) ? SHMEMX_ENOTSUP : SHMEMX_EINVAL);
@@ -1195,16 +1172,8 @@ static int fold_n(int type, int op, void *out, const void *const *ins, int nins,
     if (!out) return set_error(SHMEMX_EINVAL);
     for (int k = 0; k < nins; ++k)
         if (!ins[k]) return set_error(SHMEMX_EINVAL);
-    int done = std::min(nins, kMaxFoldInputs);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (launch(type, op, out, ins, done, nelems, s) != hipSuccess) return set_error(SHMEMX_EDEVICE);
-    while (done < nins) {
-        const void *grp[kMaxFoldInputs];
-        grp[0] = out;
-        int k = 1;
-        while (k < kMaxFoldInputs && done < nins) grp[k++] = ins[done++];
-        if (launch(type, op, out, grp, k, nelems, s) != hipSuccess) return set_error(SHMEMX_EDEVICE);
-    }
+    if (fold_groups(type, op, out, ins, nins, nelems, static_cast<hipStream_t>(stream), peers) != hipSuccess)
+        return set_error(SHMEMX_EDEVICE);
     return SHMEMX_OK;
 }
 

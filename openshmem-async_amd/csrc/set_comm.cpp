@@ -112,7 +112,7 @@ ncclComm_t set_comm(int start, int logstride, int size, int member, hipStream_t 
     auto it = cache().find(k);
     if (it != cache().end()) return it->second;
     if (!g_state.comm) fatal("set communicator", "no world RCCL communicator");
-    const int step = 1 << logstride;
+    const ActiveSet set = ActiveSet::of(start, logstride, size);
     ncclUniqueId id;
     std::memset(&id, 0, sizeof id);
     if (member == 0 && ncclGetUniqueId(&id) != ncclSuccess) fatal("set communicator", "ncclGetUniqueId failed");
@@ -124,7 +124,7 @@ ncclComm_t set_comm(int start, int logstride, int size, int member, hipStream_t 
     SHMX_NCCL(ncclGroupStart());
     if (member == 0) {
         for (int i = 1; i < size; ++i)
-            SHMX_NCCL(ncclSend(buf, sizeof id, ncclUint8, start + i * step, g_state.comm, s));
+            SHMX_NCCL(ncclSend(buf, sizeof id, ncclUint8, set.pe_of(i), g_state.comm, s));
     } else {
         SHMX_NCCL(ncclRecv(buf, sizeof id, ncclUint8, start, g_state.comm, s));
     }

@@ -1,0 +1,79 @@
+// The geometry every multi-PE algorithm shares: an active set's members, the
+// 16-byte granule, the two-shot slices, the order a member folds its inputs
+// in and the segments it gathers.  Every member of a set must compute these
+// alike (a gather reads a peer's slice where the peer's fold wrote it), so
+// each has one definition here.  Header-only and host-only, so
+// tests/native/test_set_geom.cpp checks it on the CPU.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+
+namespace shmx {
+
+// (PE_start, 1 << logPE_stride, PE_size): member i is PE start + i * step.
+struct ActiveSet {
+    int start = 0, step = 1, size = 0;
+    // a logPE_stride outside [0, 30] (refused by the set's validation, which
+    // may come later) gives step 0, which no test below takes for a stride
+    static ActiveSet of(int start, int logstride, int size) {
+        return ActiveSet{start, logstride >= 0 && logstride <= 30 ? 1 << logstride : 0, size};
+    }
+    int pe_of(int i) const { return start + i * step; }
+    // the set is the whole job (a one-member set has no stride to speak of)
+    bool world(int npes) const { return start == 0 && (step == 1 || size == 1) && size == npes; }
+};
+
+// elements per 16-byte granule
+inline size_t granule(size_t elem_size) { return elem_size >= 16 ? 1 : 16 / elem_size; }
+
+// The two-shot slices of n elements over P members: member i owns elements
+// [lo(i), hi(i)), ceil(n / P) rounded up to the granule each, so every
+// non-empty slice starts 16 bytes-aligned relative to the array; the last
+// non-empty one may be short and the ones after it are empty.
+struct Slices {
+    size_t n, slice, elem_size;
+    int P;
+    Slices(size_t n_, int P_, size_t elem_size_) : n(n_), elem_size(elem_size_), P(P_) {
+        const size_t g = granule(elem_size);
+        slice = ((n + P - 1) / P + g - 1) / g * g;
+    }
+    size_t lo(int i) const { return std::min(n, (size_t)i * slice); }
+    size_t hi(int i) const { return std::min(n, (size_t)(i + 1) * slice); }
+    size_t count(int i) const { return hi(i) - lo(i); }
+};
+
+// ins[0..P) = at(i) for the members in set order (PE_start first), or in
+// member m's own order: m first, then the others ascending
+// (reduce-op.c:219-248).
+template <class At>
+inline void fold_inputs(const void **ins, int P, int m, bool own_order, At at) {
+    int k = 0;
+    if (own_order) ins[k++] = at(m);
+    for (int i = 0; i < P; ++i)
+        if (!own_order || i != m) ins[k++] = at(i);
+}
+
+// The non-empty slices member m gathers, as byte ranges (room for P each):
+// slice i from its owner's array at base_of(i) to the same place in tgt.
+// Returns how many.  rotated: from member m + 1 on, wrapping (the gather
+// kernel gives its first blocks to its first segment, so the members start
+// on different peers' slices and no member's HBM and links take every reader
+// at once), m itself last; else ascending.  include_m: m's own slice too (its
+// target is staged).
+template <class BaseOf>
+inline int gather_segments(const Slices &sl, int m, bool rotated, bool include_m, BaseOf base_of, char *tgt,
+                           const void **from, void **to, size_t *len) {
+    int k = 0;
+    for (int r = 0; r < sl.P; ++r) {
+        const int i = rotated ? (m + 1 + r) % sl.P : r;
+        if ((i == m && !include_m) || sl.count(i) == 0) continue;
+        const size_t off = sl.lo(i) * sl.elem_size;
+        from[k] = base_of(i) + off;
+        to[k] = tgt + off;
+        len[k++] = sl.count(i) * sl.elem_size;
+    }
+    return k;
+}
+
+}  // namespace shmx

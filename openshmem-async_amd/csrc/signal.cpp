@@ -49,24 +49,11 @@
 #include "heap.h"
 #include "internal.h"
 #include "node.h"
+#include "set_geom.h"
 #include "shmem_reduce_mi355x.h"
 #include "state.h"
 
 namespace shmx {
-
-namespace {
-
-constexpr size_t kDefaultOneShotBytes = size_t(256) << 10;
-
-size_t oneshot_bytes() {
-    static const size_t b = [] {
-        const char *e = std::getenv("SHMEMX_DIRECT_ONESHOT_KB");
-        return e ? size_t(std::atol(e)) << 10 : kDefaultOneShotBytes;
-    }();
-    return b;
-}
-
-}  // namespace
 
 unsigned long long signal_timeout_ticks() {   // s_memrealtime runs at 100 MHz
     static const unsigned long long t = [] {
@@ -95,9 +82,18 @@ unsigned int signal_error() {
     return e;
 }
 
+void check_signal_error(const char *what) {
+    switch (signal_error()) {
+    case 0: break;
+    case 2: fatal(what, "a system fence before a device barrier missed an XCD");
+    default: fatal(what, "a member never reached the device barrier");
+    }
+}
+
 int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s) {
-    const int P = p.nmembers, m = p.member, step = 1 << logstride;
+    const int P = p.nmembers, m = p.member;
+    const ActiveSet set = ActiveSet::of(start, logstride, P);
     if (!node::up() || P > kMaxFoldInputs) return set_error(SHMEMX_ENOTSUP);
     const size_t sz = (size_t)p.elem_size;
     const size_t n = (size_t)nreduce;
@@ -110,26 +106,21 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     // The peers' heap segments: mapped (and voted on) the first time this set
     // meets them, plain lookups afterwards.
     std::vector<std::pair<node::Region, int>> regs;
-    for (int i = 0; i < P; ++i) regs.emplace_back(node::kHeap, start + i * step);
-    if (!map_regions(regs, start, step, P)) {
+    for (int i = 0; i < P; ++i) regs.emplace_back(node::kHeap, set.pe_of(i));
+    if (!map_regions(regs, set)) {
         trace(LOG_REDUCTION, "SIGNAL: a member could not map a peer heap (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
     SignalArgs sa;
-    if (!signal_args(start, step, P, &sa)) return set_error(SHMEMX_ENOTSUP);
+    if (!signal_args(set, &sa)) return set_error(SHMEMX_ENOTSUP);
     std::vector<char *> hb(P);
-    for (int i = 0; i < P; ++i) hb[i] = node::peer_base(node::kHeap, start + i * step);
+    for (int i = 0; i < P; ++i) hb[i] = node::peer_base(node::kHeap, set.pe_of(i));
     // every whole source, in set order, or in my own (src_me first, then
     // the other members ascending: reduce-op.c:219-248)
     const void *ins[kMaxFoldInputs];
-    {
-        int k = 0;
-        if (own_order) ins[k++] = hb[m] + soff;
-        for (int i = 0; i < P; ++i)
-            if (!own_order || i != m) ins[k++] = hb[i] + soff;
-    }
-    if (tgt != src && bytes <= oneshot_bytes() && fused_oneshot_enabled()) {
-        // barrier, fold of every whole source, barrier: one fused launch
+    fold_inputs(ins, P, m, own_order, [&](int i) { return hb[i] + soff; });
+    // a fused launch (launch_signal_fold) of these sources into my target
+    auto fused_args = [&] {
         SignalFoldArgs fa{};
         fa.sig = sa;
         fa.gsync = fence_records().gsync;
@@ -137,7 +128,11 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         for (int i = 0; i < P; ++i) fa.ins[i] = ins[i];
         fa.nins = P;
         fa.n = n;
-        SHMX_HIP(launch_signal_fold(type, op, fa, s));   // reduce-op.c:217-250
+        return fa;
+    };
+    if (tgt != src && bytes <= oneshot_bytes() && fused_oneshot_enabled()) {
+        // barrier, fold of every whole source, barrier: one fused launch
+        SHMX_HIP(launch_signal_fold(type, op, fused_args(), s));   // reduce-op.c:217-250
         count_fused_call();
         return SHMEMX_OK;
     }
@@ -168,54 +163,32 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         ws_release(s);
         return SHMEMX_OK;
     }
-    const size_t g = sz >= 16 ? 1 : 16 / sz;
-    size_t slice = (n + P - 1) / P;
-    slice = (slice + g - 1) / g * g;
-    auto lo_of = [&](int i) { return std::min(n, (size_t)i * slice); };
-    auto hi_of = [&](int i) { return std::min(n, (size_t)(i + 1) * slice); };
+    const Slices sl(n, P, sz);
+    auto tgt_of = [&](int i) { return hb[i] + toff; };
     if (bytes <= fused_twoshot_bytes()) {
         // barrier, slice fold, barrier, gather, barrier: one fused launch
-        SignalFoldArgs fa{};
-        fa.sig = sa;
-        fa.gsync = fence_records().gsync;
-        fa.out = tgt;
-        for (int i = 0; i < P; ++i) fa.ins[i] = hb[i] + soff;
-        fa.nins = P;
-        fa.n = n;
+        // (set order from here on: ins holds every source in it)
+        SignalFoldArgs fa = fused_args();
         fa.two_shot = 1;
-        fa.lo = lo_of(m);
-        fa.hi = hi_of(m);
-        for (int i = 0; i < P; ++i) {
-            if (i == m || hi_of(i) <= lo_of(i)) continue;
-            fa.gsrc[fa.nseg] = hb[i] + toff + lo_of(i) * sz;
-            fa.gdst[fa.nseg] = tgt + lo_of(i) * sz;
-            fa.glen[fa.nseg++] = (hi_of(i) - lo_of(i)) * sz;
-        }
+        fa.lo = sl.lo(m);
+        fa.hi = sl.hi(m);
+        fa.nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa.gsrc, fa.gdst, fa.glen);
         SHMX_HIP(launch_signal_fold(type, op, fa, s));   // reduce-op.c:217-250
         count_fused_twoshot_call();
         return SHMEMX_OK;
     }
     barrier();   // reduce-op.c:217
-    if (hi_of(m) > lo_of(m)) {
-        for (int i = 0; i < P; ++i) ins[i] = hb[i] + soff + lo_of(m) * sz;
-        SHMX_HIP(launch_fold_peers(type, op, tgt + lo_of(m) * sz, ins, P, hi_of(m) - lo_of(m), s));
+    if (sl.count(m) > 0) {
+        for (int i = 0; i < P; ++i) ins[i] = hb[i] + soff + sl.lo(m) * sz;
+        SHMX_HIP(launch_fold_peers(type, op, tgt + sl.lo(m) * sz, ins, P, sl.count(m), s));
     }
     barrier();   // every member's slice is final
     const void *from[kMaxFoldInputs];
     void *to[kMaxFoldInputs];
     size_t len[kMaxFoldInputs];
-    int k = 0;
-    // the segments from member m + 1 on, wrapping: the gather kernel gives
-    // its first blocks to its first segment, so member m starts on m + 1's
-    // slice and no member's HBM and links take every reader at once
-    for (int r = 1; r < P; ++r) {
-        const int i = (m + r) % P;
-        if (hi_of(i) <= lo_of(i)) continue;
-        from[k] = hb[i] + toff + lo_of(i) * sz;
-        to[k] = tgt + lo_of(i) * sz;
-        len[k++] = (hi_of(i) - lo_of(i)) * sz;
-    }
-    SHMX_HIP(launch_gather(from, to, len, k, s));
+    // from member m + 1 on, wrapping
+    const int nseg = gather_segments(sl, m, true, false, tgt_of, tgt, from, to, len);
+    SHMX_HIP(launch_gather(from, to, len, nseg, s));
     barrier();   // reduce-op.c:250
     return SHMEMX_OK;
 }

@@ -645,8 +645,7 @@ static void reduce_blocking_impl2(int type, int op, void *target, const void *so
         // retiring costs ~9 us more than the kernel's remaining time
         // (profiles/r03_latency_ab.txt).  The stream-ordered algorithms end
         // with a marker the host spins on.
-        const bool waits_itself = collective && (plan.algo == SHMEMX_ALGO_DIRECT ||
-                                                 (plan.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only));
+        const bool waits_itself = collective && pulls_over_ipc(plan);
         if (rc == SHMEMX_OK && (!waits_itself || g_state.settle_dst)) {
             const HostSignal sig = next_host_signal();
             if (g_state.settle_dst) {
@@ -662,11 +661,7 @@ static void reduce_blocking_impl2(int type, int op, void *target, const void *so
         } else if (rc != SHMEMX_OK) {
             SHMX_HIP(hipStreamSynchronize(s));
         }
-        switch (signal_error()) {
-        case 0: break;
-        case 2: fatal("SIGNAL reduction", "a system fence before a device barrier missed an XCD");
-        default: fatal("SIGNAL reduction", "a member never reached the device barrier");
-        }
+        check_signal_error("SIGNAL reduction");
         return;
     }
     // Host-resident symmetric arrays (the reference's heap): stage over PCIe
@@ -731,8 +726,7 @@ static void reduce_blocking_impl2(int type, int op, void *target, const void *so
         // result into bout over PCIe, and the call returns with its work
         // done, so the copy kernels on either side and the extra wait go.
         // RCCL's algorithms need device memory: they keep the staging copies.
-        const bool pulls = collective && (plan.algo == SHMEMX_ALGO_DIRECT ||
-                                          (plan.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only));
+        const bool pulls = collective && pulls_over_ipc(plan);
         const void *dsrc = source;
         if (!sdev) {
             std::memcpy(bin, source, bytes);
@@ -763,11 +757,7 @@ static void reduce_blocking_impl2(int type, int op, void *target, const void *so
         } else {
             SHMX_HIP(hipStreamSynchronize(s));
         }
-        switch (signal_error()) {
-        case 0: break;
-        case 2: fatal("SIGNAL reduction", "a system fence before a device barrier missed an XCD");
-        default: fatal("SIGNAL reduction", "a member never reached the device barrier");
-        }
+        check_signal_error("SIGNAL reduction");
         if (!rc && !tdev) std::memcpy(target, bout, bytes);
         return;
     }
@@ -776,7 +766,7 @@ static void reduce_blocking_impl2(int type, int op, void *target, const void *so
         SHMX_HIP(hipStreamCreateWithFlags(&g_state.d2h, hipStreamNonBlocking));
     }
     const size_t sz = type_size(type);
-    const size_t g = sz >= 16 ? 1 : 16 / sz;
+    const size_t g = granule(sz);
     static const size_t stage_chunk = [] {
         const char *e = std::getenv("SHMEMX_STAGE_CHUNK_MB");
         const int mb = e ? std::atoi(e) : 0;

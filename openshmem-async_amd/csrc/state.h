@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>
 
 #include "node.h"
+#include "set_geom.h"
 #include "shmem_reduce_mi355x.h"
 
 #include <chrono>
@@ -166,8 +167,21 @@ void device_sync();       // service_quiesce, then hipDeviceSynchronize
 // The plan of one call (shmemx_reduce_plan) and the device-resident engine
 // (runtime.cpp); the host staging of the blocking entry points (staging.cpp)
 // runs the engine chunk by chunk.
+// What the planner must know of a call that is being captured into a
+// hipGraph (reduce_device fills it in; the other callers plan plain calls).
+// Every PE of a set must capture its calls alike, as for every
+// stream-ordered collective.
+struct PlanCapture {
+    // an AUTO call under capture: the table's DIRECT (host barriers, refused
+    // under capture) falls back to the built-in rule, so the call still plans
+    bool auto_algo = false;
+    // a call under capture (AUTO, or on a partial set): a set whose RCCL
+    // communicator does not exist yet cannot take an RCCL algorithm
+    // (creating one is not a stream operation)
+    bool no_new_comm = false;
+};
 int make_plan(int type, int op, int nreduce, int start, int logstride, int size, int pe, int npes,
-              int algo, shmemx_plan_t *p);
+              int algo, shmemx_plan_t *p, PlanCapture cap = {});
 int reduce_device(int type, int op, void *target, const void *source, int nreduce, int start,
                   int logstride, int size, int algo, hipStream_t s);
 bool overlap(const void *a, const void *b, size_t bytes);   // distinct, overlapping ranges
@@ -195,6 +209,16 @@ void fold_chain(int type, int op, void *out, const void **ins, int nins, size_t 
 int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s);
 void direct_release();
+// This plan pulls over IPC mappings and returns with its work done (host
+// barriers, or the fused launch's host signal): DIRECT, and own-order GATHER
+// on the IPC transport.
+inline bool pulls_over_ipc(const shmemx_plan_t &p) {
+    return p.algo == SHMEMX_ALGO_DIRECT || (p.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only);
+}
+// Arrays up to this size take DIRECT's and SIGNAL's one shot
+// ($SHMEMX_DIRECT_ONESHOT_KB, default 256 KiB; every PE must agree).
+constexpr size_t kDefaultOneShotBytes = size_t(256) << 10;
+size_t oneshot_bytes();
 // This PE's IPC scratch region (allocated and published on first use).
 char *ipc_scratch(size_t *bytes);
 // System-scope fence on every XCD (launch_sys_fence), then wait for stream s;
@@ -213,7 +237,7 @@ FenceRecords fence_records();
 // SignalArgs for the members of a set over their mapped heap segments (the
 // signal counters at heap::signal_offset()); false if this PE has no heap
 // segment or a member's segment is not mapped.
-bool signal_args(int start, int step, int P, SignalArgs *sa);
+bool signal_args(const ActiveSet &set, SignalArgs *sa);
 // A one-shot reduction as one fused launch (launch_signal_fold): count it in
 // shmemx_direct_stats.
 void count_fused_call();
@@ -242,7 +266,7 @@ void node_done(int start, int step, int P, hipStream_t s, double *stream_us = nu
 // Map the peers' regions a collective reads (node::peer_base), voting across
 // the set the first time a combination is met; false on every member alike
 // if any member failed (direct.cpp).
-bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, int start, int step, int P);
+bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set);
 // SIGNAL algorithm (signal.cpp): DIRECT's pulls with device-side barriers,
 // stream-ordered and graph-capturable; symmetric-heap operands only.
 // own_order: every member folds the whole array in its own reference order.
@@ -251,6 +275,8 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
 // After the stream has drained: 0, or 1 if a SIGNAL barrier timed out, 2 if
 // a fence before one missed an XCD.  (Clears it.)
 unsigned int signal_error();
+// The same, for a blocking call whose stream has drained: a set error is FATAL.
+void check_signal_error(const char *what);
 // The host-mapped error word the device barriers set, and their timeout in
 // s_memrealtime ticks ($SHMEMX_SIGNAL_TIMEOUT).
 unsigned int *signal_error_word();
