@@ -317,6 +317,41 @@ int shmemx_fold_n_peers_on_stream(int type, int op, void *out,
 int shmemx_gather_on_stream(const void *const *srcs, void *const *dsts,
                             const size_t *bytes, int nseg, void *stream);
 
+/* Test hook: the fused SIGNAL / DIRECT launches on one GPU, with no heap and
+ * no peers.  Runs member m's launch of a P-member set (P <= 16) whose
+ * members' sources srcs[i] and targets tgts[i] are all device arrays of the
+ * calling process, on `stream`, and waits for it (blocking).
+ *   schedule 0  the fused one shot: tgts[m] = fold of every whole source, in
+ *               set order, or in m's own order (m first, then the others
+ *               ascending) with own_order != 0;
+ *   schedule 1  the fused two shot, set up as a SIGNAL call sets it up: m
+ *               folds its slice of every source into tgts[m], then copies
+ *               every other member's slice from tgts[i] to the same place in
+ *               tgts[m] (own_order must be 0);
+ *   schedule 2  the unfused device barrier alone (the system fence, then the
+ *               signal wave); tgts, srcs and nelems are ignored.
+ * What loops back is the peer handshake only: the launch is PE 0 of PEs
+ * 0..P-1 over a private, zeroed signal area in which every "peer's counter
+ * for me" is the very word the launch has just bumped for that peer, so
+ * every wait is satisfied by the launch's own store.  The grid barrier, the
+ * fences, the XCD-coverage check (counted in shmemx_direct_stats), the fold
+ * and the gather run as in a multi-PE call.  A barrier that does not
+ * complete gives up after 2 s.  The launch shares the device-side barrier
+ * state of the SIGNAL and DIRECT algorithms: no SIGNAL or DIRECT call may be
+ * in flight on this GPU.  Needs no shmem_init; the current device is treated
+ * as by the local folds above.
+ * *signal_error (may be NULL) receives the device barriers' error word after
+ * the launch (0; 1 a wait timed out; 2 a fence missed an XCD), which is
+ * cleared.  Returns OK (at once, for nelems == 0 with schedule 0 or 1);
+ * EDEVICE for a failed launch, a non-zero error word, or a tiny one shot
+ * (nelems <= 1024) whose host signal did not arrive; EINVAL, before any HIP
+ * call, for a pair the reference lacks, schedule outside 0..2, P outside
+ * 1..16, m outside 0..P-1, own_order with schedule 1, or, for schedules 0
+ * and 1 with nelems > 0, NULL tgts / srcs or a NULL entry. */
+int shmemx_fused_loopback(int type, int op, int schedule, int P, int m, int own_order,
+                          void *const *tgts, const void *const *srcs, size_t nelems,
+                          unsigned int *signal_error, void *stream);
+
 /* Register (on != 0) or deregister the symmetric heap's HBM segment with
  * the library's RCCL communicator (ncclCommRegister), so RCCL may use
  * collectives' heap operands in place instead of staging them through its

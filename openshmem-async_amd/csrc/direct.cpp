@@ -159,6 +159,7 @@ struct FenceState {
     unsigned int *dev_seen = nullptr;          // device, kFenceBlocks words
     unsigned long long *dev_stats = nullptr;   // device: [checks, incomplete]
     unsigned int *gsync = nullptr;             // device: fused kernel's grid barrier
+    unsigned long long *loopback = nullptr;    // device: shmemx_fused_loopback's counters
     int nxcc = 0;
     double host_checks = 0, host_refills = 0;
 } g_fence;
@@ -235,6 +236,22 @@ void fence_and_wait(hipStream_t s) {
 FenceRecords fence_records() {
     ensure_fence();
     return FenceRecords{g_fence.dev_seen, g_fence.nxcc, g_fence.dev_stats, g_fence.gsync};
+}
+
+unsigned long long *loopback_signal_area() {
+    ensure_fence();
+    if (!g_fence.loopback) {
+        void *p = nullptr;
+        const size_t bytes = kMaxFoldInputs * sizeof(unsigned long long);
+        if (hipMalloc(&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) {
+            (void)hipGetLastError();
+            if (p) (void)hipFree(p);
+            return nullptr;
+        }
+        g_fence.loopback = static_cast<unsigned long long *>(p);
+    }
+    return g_fence.loopback;
 }
 
 void node_sync(int start, int step, int P, hipStream_t s, double *stream_us, double *barrier_us,
@@ -359,6 +376,7 @@ void direct_release() {
         (void)hipFree(g_fence.dev_seen);
         (void)hipFree(g_fence.dev_stats);
         (void)hipFree(g_fence.gsync);
+        if (g_fence.loopback) (void)hipFree(g_fence.loopback);
         g_fence = FenceState{};
     }
     if (!g_scratch.base) return;

@@ -1127,28 +1127,7 @@ int shmemx_reduce_on_stream(int type, int op, void *target, const void *source,
                             logPE_stride, PE_size, algo, stream);
 }
 
-// The local folds need no shmem_init (they run on the caller's stream) and
-// leave the calling thread's current device as they found it: a
-// caller's stream carries its own device; after shmem_init a NULL stream
-// means the PE's device, made current for the launch and then restored.
-class LocalDevice {
-  public:
-    explicit LocalDevice(void *stream) {
-        if (stream || !g_state.inited) return;
-        if (hipGetDevice(&prev_) != hipSuccess || prev_ == g_state.device) {
-            prev_ = -1;
-            return;
-        }
-        SHMX_HIP(hipSetDevice(g_state.device));
-    }
-    ~LocalDevice() {
-        if (prev_ >= 0) (void)hipSetDevice(prev_);
-    }
-
-  private:
-    int prev_ = -1;
-};
-
+// The local folds need no shmem_init: LocalDevice (state.h).
 int shmemx_fold_on_stream(int type, int op, void *acc, const void *in,
                           size_t nelems, void *stream) {
     t_last_error = SHMEMX_OK;

@@ -90,6 +90,34 @@ void check_signal_error(const char *what) {
     }
 }
 
+namespace {
+
+// A fused launch (launch_signal_fold) of the P sources ins into out: the one
+// shot as it stands, the two shot after two_shot_args.
+SignalFoldArgs fused_args(const SignalArgs &sa, void *out, const void *const *ins, int P, size_t n) {
+    SignalFoldArgs fa{};
+    fa.sig = sa;
+    fa.gsync = fence_records().gsync;
+    fa.out = out;
+    for (int i = 0; i < P; ++i) fa.ins[i] = ins[i];
+    fa.nins = P;
+    fa.n = n;
+    return fa;
+}
+
+// The fused two shot of member m: fold slice m (set order: fa->ins holds
+// every source in it), then gather the other non-empty slices, ascending,
+// from the members' targets tgt_of(i) into tgt.
+template <class TgtOf>
+void two_shot_args(SignalFoldArgs *fa, const Slices &sl, int m, TgtOf tgt_of, char *tgt) {
+    fa->two_shot = 1;
+    fa->lo = sl.lo(m);
+    fa->hi = sl.hi(m);
+    fa->nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa->gsrc, fa->gdst, fa->glen);
+}
+
+}  // namespace
+
 int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s) {
     const int P = p.nmembers, m = p.member;
@@ -119,20 +147,9 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     // the other members ascending: reduce-op.c:219-248)
     const void *ins[kMaxFoldInputs];
     fold_inputs(ins, P, m, own_order, [&](int i) { return hb[i] + soff; });
-    // a fused launch (launch_signal_fold) of these sources into my target
-    auto fused_args = [&] {
-        SignalFoldArgs fa{};
-        fa.sig = sa;
-        fa.gsync = fence_records().gsync;
-        fa.out = tgt;
-        for (int i = 0; i < P; ++i) fa.ins[i] = ins[i];
-        fa.nins = P;
-        fa.n = n;
-        return fa;
-    };
     if (tgt != src && bytes <= oneshot_bytes() && fused_oneshot_enabled()) {
         // barrier, fold of every whole source, barrier: one fused launch
-        SHMX_HIP(launch_signal_fold(type, op, fused_args(), s));   // reduce-op.c:217-250
+        SHMX_HIP(launch_signal_fold(type, op, fused_args(sa, tgt, ins, P, n), s));   // reduce-op.c:217-250
         count_fused_call();
         return SHMEMX_OK;
     }
@@ -168,11 +185,8 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     if (bytes <= fused_twoshot_bytes()) {
         // barrier, slice fold, barrier, gather, barrier: one fused launch
         // (set order from here on: ins holds every source in it)
-        SignalFoldArgs fa = fused_args();
-        fa.two_shot = 1;
-        fa.lo = sl.lo(m);
-        fa.hi = sl.hi(m);
-        fa.nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa.gsrc, fa.gdst, fa.glen);
+        SignalFoldArgs fa = fused_args(sa, tgt, ins, P, n);
+        two_shot_args(&fa, sl, m, tgt_of, tgt);
         SHMX_HIP(launch_signal_fold(type, op, fa, s));   // reduce-op.c:217-250
         count_fused_twoshot_call();
         return SHMEMX_OK;
@@ -194,3 +208,75 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
 }
 
 }  // namespace shmx
+
+using namespace shmx;
+
+// Test hook: member m's launch of a P-member set whose members' arrays all
+// belong to this process, with the peer handshakes looped back onto the
+// launch's own counters (peer[i] + me is the word mine + pe[i] it has just
+// bumped), so the grid barrier, the fences, the XCD-coverage check, the fold
+// and the gather run for real on one GPU with no heap and no peers.
+extern "C" int shmemx_fused_loopback(int type, int op, int schedule, int P, int m, int own_order,
+                                     void *const *tgts, const void *const *srcs, size_t nelems,
+                                     unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!op_valid(type, op) || schedule < 0 || schedule > 2 || P < 1 || P > kMaxFoldInputs || m < 0 ||
+        m >= P || (own_order && schedule == 1))
+        return set_error(SHMEMX_EINVAL);
+    if (!op_on_device(type, op)) return set_error(SHMEMX_ENOTSUP);
+    if (schedule != 2) {
+        if (nelems == 0) return SHMEMX_OK;
+        if (!tgts || !srcs) return set_error(SHMEMX_EINVAL);
+        for (int i = 0; i < P; ++i)
+            if (!tgts[i] || !srcs[i]) return set_error(SHMEMX_EINVAL);
+    }
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalArgs sa{};
+    sa.mine = loopback_signal_area();
+    if (!sa.mine) return set_error(SHMEMX_ENOMEM);
+    sa.P = P;
+    sa.me = 0;
+    for (int i = 0; i < P; ++i) {
+        sa.pe[i] = i;
+        sa.peer[i] = sa.mine + i;
+    }
+    // a bound, not a tuned number: a broken barrier ends the kernel in
+    // seconds (2 s of the 100 MHz clock), not at $SHMEMX_SIGNAL_TIMEOUT
+    sa.timeout_ticks = 200000000ull;
+    sa.err = signal_error_word();
+    const FenceRecords fr = fence_records();
+    sa.seen = fr.seen;
+    sa.nxcc = fr.nxcc;
+    sa.fence_stats = fr.stats;
+    hipError_t e = hipSuccess;
+    HostSignal sig{nullptr, 0};
+    if (schedule == 2) {
+        e = launch_sys_fence(s, sa.seen);
+        if (e == hipSuccess) e = launch_signal(sa, s);
+    } else {
+        const void *ins[kMaxFoldInputs];
+        fold_inputs(ins, P, m, own_order != 0, [&](int i) { return srcs[i]; });
+        char *const tgt = static_cast<char *>(tgts[m]);
+        SignalFoldArgs fa = fused_args(sa, tgt, ins, P, nelems);
+        if (schedule == 1) {
+            const Slices sl(nelems, P, type_size(type));
+            two_shot_args(&fa, sl, m, [&](int i) { return static_cast<char *>(tgts[i]); }, tgt);
+        } else if (nelems <= kFusedTinyElems) {
+            // the tiny one shot tells the host itself, as under DIRECT
+            sig = next_host_signal();
+            fa.host_word = sig.word;
+            fa.host_value = sig.value;
+        }
+        e = launch_signal_fold(type, op, fa, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    if (sig.word && *static_cast<volatile unsigned long long *>(sig.word) != sig.value)
+        return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}

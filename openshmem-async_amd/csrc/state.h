@@ -124,6 +124,28 @@ int ensure_init();                  // single-PE auto-init; ENOINIT if npes > 1
 // device current first, so a thread other than shmem_init's does not make
 // them on device 0 (one PE per GPU: LOCAL_RANK > 0 is never device 0).
 void bind_device();
+// The local folds and the test hooks next to them need no shmem_init (they
+// run on the caller's stream) and leave the calling thread's current device
+// as they found it: a caller's stream carries its own device;
+// after shmem_init a NULL stream means the PE's device, made current for the
+// launch and then restored.
+class LocalDevice {
+  public:
+    explicit LocalDevice(void *stream) {
+        if (stream || !g_state.inited) return;
+        if (hipGetDevice(&prev_) != hipSuccess || prev_ == g_state.device) {
+            prev_ = -1;
+            return;
+        }
+        SHMX_HIP(hipSetDevice(g_state.device));
+    }
+    ~LocalDevice() {
+        if (prev_ >= 0) (void)hipSetDevice(prev_);
+    }
+
+  private:
+    int prev_ = -1;
+};
 // Members-only RCCL communicators of partial active sets (set_comm.cpp):
 // set_comm returns the set's cached communicator, creating it first (a
 // collective over the set's members alone: `member` is this PE's index in it)
@@ -234,6 +256,10 @@ struct FenceRecords {
     unsigned int *gsync;   // the fused one-shot kernel's grid barrier (2 words)
 };
 FenceRecords fence_records();
+// shmemx_fused_loopback's private signal area (signal.cpp): kMaxFoldInputs
+// zeroed counters in device memory, allocated on first use and released with
+// direct_release; nullptr if the allocation failed.
+unsigned long long *loopback_signal_area();
 // SignalArgs for the members of a set over their mapped heap segments (the
 // signal counters at heap::signal_offset()); false if this PE has no heap
 // segment or a member's segment is not mapped.

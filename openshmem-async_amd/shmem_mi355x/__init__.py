@@ -114,6 +114,9 @@ def lib() -> ctypes.CDLL:
     L.shmemx_gather_on_stream.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp),
                                           ctypes.POINTER(sz), i, vp]
     L.shmemx_gather_on_stream.restype = i
+    L.shmemx_fused_loopback.argtypes = [i, i, i, i, i, i, ctypes.POINTER(vp), ctypes.POINTER(vp), sz,
+                                        ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_fused_loopback.restype = i
     L.shmemx_reduce_plan.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(Plan)]
     L.shmemx_reduce_plan.restype = i
     L.shmemx_get_uniqueid.argtypes = [vp]
@@ -326,6 +329,26 @@ def gather(srcs, dsts, nbytes, stream: int = 0) -> None:
     b = (ctypes.c_void_p * k)(*[addr(x) for x in dsts])
     c = (ctypes.c_size_t * k)(*nbytes)
     _check(lib().shmemx_gather_on_stream(a, b, c, k, stream or None), "shmemx_gather_on_stream")
+
+
+def fused_loopback(type_name: str, op: str, schedule: int, tgts, srcs, nelems: int, m: int = 0,
+                   own_order: bool = False, stream: int = 0) -> int:
+    """shmemx_fused_loopback: member m's fused one-shot (schedule 0) or
+    two-shot (1) launch, or the unfused device barrier (2), of a
+    len(tgts)-member set whose arrays are all this process's, with the peer
+    handshakes looped back.  Blocking.  Returns the device barriers' error
+    word (0 when the call returned OK)."""
+    P = len(tgts)
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in tgts])
+    b = (ctypes.c_void_p * len(srcs))(*[addr(x) for x in srcs])
+    if len(srcs) != P:
+        raise ValueError("one source per target")
+    err = ctypes.c_uint(0)
+    rc = lib().shmemx_fused_loopback(TYPES[type_name], OPS[op], schedule, P, m, 1 if own_order else 0,
+                                     a, b, nelems, ctypes.byref(err), stream or None)
+    _check(rc, f"shmemx_fused_loopback({type_name},{op},schedule={schedule},P={P},m={m}): "
+               f"error word {err.value}")
+    return err.value
 
 
 @dataclass

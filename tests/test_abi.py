@@ -310,6 +310,49 @@ def test_fold_n_argument_errors_without_a_device(shm, peers):
     assert fn(T["double"], O["sum"], 8, ins, 2, 0, None) == 0             # zero elements
 
 
+def test_fused_loopback_argument_errors_without_a_device(shm):
+    """shmemx_fused_loopback rejects bad arguments before touching HIP: EINVAL
+    for a pair the reference lacks, a schedule outside 0..2, P outside 1..16,
+    m outside 0..P-1, own order with the two shot, and NULL arrays or a NULL
+    entry when there are elements; nothing to do for zero elements."""
+    import ctypes
+    fn = shm.lib().shmemx_fused_loopback
+    D, I = shm.TYPES["double"], shm.TYPES["int"]
+    SUM, XOR, MIN = shm.OPS["sum"], shm.OPS["xor"], shm.OPS["min"]
+    good = (ctypes.c_void_p * 16)(*([64] * 16))
+    hole = (ctypes.c_void_p * 16)(*([64] * 5 + [None] + [64] * 10))
+    err = ctypes.c_uint(7)
+    for schedule in (0, 1, 2):
+        assert fn(D, XOR, schedule, 3, 0, 0, good, good, 16, err, None) == 1       # not a reference pair
+        assert fn(shm.TYPES["complexd"], MIN, schedule, 3, 0, 0, good, good, 16, err, None) == 1
+        assert fn(99, SUM, schedule, 3, 0, 0, good, good, 16, err, None) == 1
+        for P in (0, -1, 17):
+            assert fn(D, SUM, schedule, P, 0, 0, good, good, 16, err, None) == 1   # P outside 1..16
+        for P, m in ((3, -1), (3, 3), (16, 16), (1, 1)):
+            assert fn(D, SUM, schedule, P, m, 0, good, good, 16, err, None) == 1   # m outside 0..P-1
+    for schedule in (-1, 3):
+        assert fn(D, SUM, schedule, 3, 0, 0, good, good, 16, err, None) == 1
+    assert fn(D, MIN, 1, 3, 0, 1, good, good, 16, err, None) == 1                  # own order, two shot
+    assert fn(D, MIN, 1, 3, 0, 1, good, good, 0, err, None) == 1
+    for schedule in (0, 1):
+        assert fn(D, SUM, schedule, 3, 0, 0, None, good, 16, err, None) == 1       # NULL arrays
+        assert fn(D, SUM, schedule, 3, 0, 0, good, None, 16, err, None) == 1
+        assert fn(D, SUM, schedule, 6, 0, 0, hole, good, 16, err, None) == 1       # a NULL entry
+        assert fn(I, XOR, schedule, 6, 2, 0, good, hole, 16, err, None) == 1
+        # zero elements: nothing to do, whatever the arrays
+        assert fn(D, SUM, schedule, 3, 2, 0, good, good, 0, err, None) == 0
+        assert fn(D, SUM, schedule, 6, 0, 0, hole, None, 0, None, None) == 0
+    assert fn(D, MIN, 0, 16, 15, 1, good, good, 0, err, None) == 0                 # own order, one shot
+    assert shm.last_error() == 0
+    assert err.value == 7        # never written before a launch
+    with pytest.raises(shm.ShmemError) as e:
+        shm.fused_loopback("double", "sum", 1, [64, 64], [64, 0], 8, m=1)
+    assert e.value.code == 1
+    with pytest.raises(ValueError):
+        shm.fused_loopback("double", "sum", 0, [64, 64], [64], 8)
+    assert shm.fused_loopback("double", "sum", 0, [64, 64], [64, 64], 0) == 0
+
+
 def test_fused_twoshot_limit_setter(shm):
     """shmemx_set_fused_twoshot_kb returns the previous limit (the 4 MiB
     default unless $SHMEMX_FUSED_TWOSHOT_KB says otherwise) and refuses a
