@@ -37,9 +37,6 @@ struct State {
     // another PE process of the job uses this GPU (node::gpu_shared): the
     // service workgroup stays off unless $SHMEMX_SERVICE=1 (service.hip)
     bool gpu_shared = false;
-    // a mirrored-heap source's current host-view bytes, for the exchange
-    // (staging.cpp reduce_blocking; its HBM twin is not flushed)
-    const void *xchg_src_host = nullptr;
     // the heap segment registered with the RCCL communicator
     // (shmemx_rccl_register_heap), or nullptr
     void *rccl_reg = nullptr;
@@ -49,8 +46,9 @@ struct State {
     // communicator and runs the collective schedules, so a one-GPU box can
     // execute every RCCL call of the path
     bool force_collective = false;
-    // inside a blocking entry point: wait_host_signal returns as soon as the
-    // work's host signal arrives, without seeing the stream idle
+    // inside a blocking entry point (staging.cpp reduce_blocking sets it for
+    // the call): wait_host_signal returns as soon as the work's host signal
+    // arrives, without seeing the stream idle
     bool return_on_signal = false;
     // the library stream may hold work nobody has waited for: a
     // stream-ordered call enqueued on it (cleared when a blocking call's own
@@ -61,12 +59,6 @@ struct State {
     // completion by microseconds.
     bool lib_stream_dirty = false;
     bool lib_stream_exported = false;
-    // inside a blocking call on a small host-view target (staging.cpp): the
-    // device address where the call's last kernel also stores the result (the
-    // view's page-locked alias, heap.h DeviceWrite::settle_dst), and whether
-    // it did, before the host signal
-    void *settle_dst = nullptr;
-    bool settled = false;
     // grow-only device workspaces
     void *ws = nullptr;        // A2A shard receive area / GATHER sources
     size_t ws_bytes = 0;
@@ -160,11 +152,10 @@ ncclComm_t set_comm(int start, int logstride, int size, int member, hipStream_t 
 bool set_comm_prepare(int start, int logstride, int size, int member, hipStream_t s);
 bool set_comm_refused(int start, int logstride, int size);
 void set_comms_release();
-// memcpy split over the staging pool's CPU threads (staging.cpp); a caller
-// that finds the pool busy copies alone (the mirrored heap's fault handler
+// memcpy split over the staging copy threads (staging.cpp, copy_gang.h); a
+// caller that finds them busy copies alone (the mirrored heap's fault handler
 // uses it too)
-// nt: streaming (non-temporal) stores, for a destination nothing reads soon
-void parallel_copy(void *dst, const void *src, size_t bytes, bool nt = false);
+void parallel_copy(void *dst, const void *src, size_t bytes);
 void ring_free();   // the staging ring (staging.cpp), at finalize
 int gpu_numa_node(int device);   // NUMA node of a HIP device's PCI function, or -1
 // The resident service workgroup (service.hip): a small one-member blocking

@@ -32,6 +32,13 @@ static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
  * TSan must report (the negative control of tests/test_gpu_tsan.py) */
 static volatile long racy;
 static int negative;
+/* The workers meet right before they write it, so nothing orders one write
+ * before the other.  Without that, one worker's write, its count() and a
+ * world call of the main thread (which takes count()'s mutex, then the
+ * library's lock) could all come before another worker's last library call:
+ * a happens-before chain, and no race, whenever the main thread was still
+ * making world calls at that time. */
+static pthread_barrier_t meet;
 
 static void fail(int w, int line, const char *what) {
     pthread_mutex_lock(&mu);
@@ -115,7 +122,10 @@ static void *worker(void *arg) {
             for (int i = 0; i < HEAP_N && ok; ++i) ok = wk->heap_tgt[i] == (long)i * 11 + w * 7 + it;
             CHECK(ok, "heap view");
         }
-        if (negative) racy = racy + w + 1;
+        if (negative) {
+            pthread_barrier_wait(&meet);
+            racy = racy + w + 1;
+        }
         count(3);
     }
     free(dh);
@@ -144,6 +154,7 @@ int main(int argc, char **argv) {
         wk[w].heap_tgt = mirrored ? shmem_align(65536, HEAP_N * sizeof(long)) : NULL;
     }
     int *wsrc = shmem_malloc(1024 * sizeof(int)), *wtgt = shmem_malloc(1024 * sizeof(int));
+    if (negative) pthread_barrier_init(&meet, NULL, nthreads < 16 ? nthreads : 16);
     for (int w = 0; w < nthreads && w < 16; ++w) pthread_create(&th[w], NULL, worker, &wk[w]);
     const int w = -1;
     for (int c = 0; c < 40; ++c) {   /* world calls while the workers run */

@@ -4,7 +4,8 @@ fails the run): the symmetric-heap arena (arena.cpp), the intra-node block's
 host barrier and descriptors over forked PEs (node.cpp), the soft x87
 arithmetic the GPU runs for long double (ld80.h), and the copy threads'
 placement over a fake sysfs tree (topology.cpp), the staging chunk
-schedule (stage_plan.h) and the active-set geometry (set_geom.h).  The same harnesses run
+schedule (stage_plan.h), the active-set geometry (set_geom.h) and the staging
+copy gang (copy_gang.h, also under ThreadSanitizer).  The same harnesses run
 unsanitized, at larger sizes, in test_heap_host.py, test_node_host.py and
 test_ld80_host.py.  GPU-side sanitizers are not available on the MI355X pool."""
 import os
@@ -32,6 +33,8 @@ CASES = {
     # the copy threads' placement (staging.cpp: cache domains of the GPU's node)
     "topology": ([os.path.join(NATIVE, "test_topology.cpp"), os.path.join(CSRC, "topology.cpp")], [],
                  ["{tmp}/sys"], "ok "),
+    # the staging copies: the streaming copy and the thread gang (copy_gang.h)
+    "copy_gang": ([os.path.join(NATIVE, "test_copy_gang.cpp")], ["-pthread"], [], "ok "),
 }
 
 
@@ -48,6 +51,20 @@ def test_host_code_under_asan_ubsan(tmp_path, name):
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert out.stdout.startswith(want), out.stdout[-2000:]
     assert "runtime error" not in out.stderr, out.stderr[-4000:]
+
+
+def test_copy_gang_under_tsan(tmp_path):
+    """The same stand-alone program under ThreadSanitizer (gcc): the gang's
+    hand-over of a copy to its workers and back, two gangs at once, and two
+    threads in copy() at once, with no data race reported."""
+    exe = tmp_path / "copy_gang_tsan"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-I", CSRC,
+                    os.path.join(NATIVE, "test_copy_gang.cpp"), "-pthread", "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66"))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.startswith("ok "), out.stdout[-2000:]
+    assert "ThreadSanitizer" not in out.stderr, out.stderr[-4000:]
 
 
 def test_gpu_asan_build_is_instrumented():
