@@ -232,16 +232,34 @@ enum {
  *           launch.  A peer that never arrives
  *           times out after $SHMEMX_SIGNAL_TIMEOUT s (default 20); the next
  *           blocking call then aborts with a FATAL line.
+ *   OWNSLICE  opt-in, for the six own-order pairs (below) at two-shot cost:
+ *           member m reads slice m of every member's source (as DIRECT's
+ *           first phase) and folds it in all P orders at once, one result
+ *           per member: its own into slice m of its own target, the others
+ *           into P-1 slots of its IPC scratch region.  After a host barrier
+ *           member k copies "its" result of every other slice from the
+ *           owners' slots into its target (one gather launch).  2(P-1)/P of
+ *           the array crosses xGMI per PE, as reads only, against (P-1)x
+ *           for the other algorithms on these pairs; workspace (P-1) slices
+ *           of scratch, no allocation.  Each PE's own reference bits.  Any
+ *           set of 2..16 PEs, both transports, host-synchronous; operands
+ *           anywhere (a source outside the heap or partially overlapping
+ *           the target is staged through scratch, as DIRECT's).  Arrays up
+ *           to $SHMEMX_DIRECT_ONESHOT_KB take DIRECT's own-order one shot.
+ *           Every other pair, and a one-member set, plans and runs as
+ *           DIRECT, so it may be set job-wide.  AUTO never chooses it.
  * With $SHMEMX_TRANSPORT=ipc there is no RCCL communicator: AUTO means
  * DIRECT, GATHER runs as a DIRECT-style kernel in each PE's own order, and
  * RCCL / A2A / ALLREDUCE are ENOTSUP; SIGNAL runs on both transports.
  * Float, double and long double min / max: a<b?a:b under NaN and +-0 gives
  * each PE its own reference answer (reduce-op.c:130-142, 219-248), so on
  * these six pairs every algorithm folds in the calling PE's own order: A2A
- * runs as GATHER, DIRECT and SIGNAL read every member's whole source. */
+ * runs as GATHER, DIRECT and SIGNAL read every member's whole source;
+ * OWNSLICE has each slice's owner fold it in every member's order. */
 enum {
     SHMEMX_ALGO_AUTO = 0, SHMEMX_ALGO_RCCL, SHMEMX_ALGO_A2A,
     SHMEMX_ALGO_GATHER, SHMEMX_ALGO_ALLREDUCE, SHMEMX_ALGO_DIRECT, SHMEMX_ALGO_SIGNAL,
+    SHMEMX_ALGO_OWNSLICE,
     SHMEMX_NALGOS
 };
 
@@ -271,7 +289,8 @@ int shmemx_initialized(void);
 void *shmemx_get_stream(void);
 
 /* Algorithm used by the entry points (default AUTO, or $SHMEM_REDUCE_ALGO =
- * auto|rccl|a2a|gather|allreduce|direct).  Returns the previous value. */
+ * auto|rccl|a2a|gather|allreduce|direct|signal|ownslice).  Returns the
+ * previous value. */
 int shmemx_set_algo(int algo);
 
 /* Stream-ordered reduction: enqueue on `stream` (hipStream_t; NULL = the
@@ -303,6 +322,23 @@ int shmemx_fold_n_on_stream(int type, int op, void *out,
 int shmemx_fold_n_peers_on_stream(int type, int op, void *out,
                                   const void *const *ins, int nins, size_t nelems,
                                   void *stream);
+
+/* The P-order fold: nins inputs, nins outputs, one pass,
+ *   outs[k][i] = op(...op(op(ins[k][i], ins[j0][i]), ins[j1][i])...)
+ * with j ascending over the other inputs: for every k at once, the order in
+ * which member k of a set folds (its own source first, reduce-op.c:219-248).
+ * For the six pairs whose answer depends on that order (float, double and
+ * long double min / max): ENOTSUP for any other reference pair.  outs[k] may
+ * be exactly ins[k] (every lane loads all inputs of a vector before storing
+ * any output of it); EINVAL for any other overlap between an output and an
+ * input or another output, for nins outside 1..16, a pair the reference
+ * lacks, or, with nelems > 0, NULL arrays or entries: all before any HIP
+ * call.  nelems == 0 launches nothing.  Device pointers, stream-ordered;
+ * device and shmem_init as for the local folds above.  OWNSLICE's first
+ * phase; the kernel clock reports it as kind 4. */
+int shmemx_fold_orders_on_stream(int type, int op, void *const *outs,
+                                 const void *const *ins, int nins,
+                                 size_t nelems, void *stream);
 
 /* DIRECT's all-gather step as one launch: nseg (<= 16) byte ranges
  * srcs[i] -> dsts[i] copied concurrently (consecutive runs of up to 256
@@ -365,12 +401,12 @@ int shmemx_rccl_register_heap(int on);
 
 /* The kernel clock: with on != 0, every launch of the fold family (the
  * 2-input and P-input folds, the copy of a one-member call, the peers fold,
- * the gather) carries start / stop events of its own dispatch
+ * the gather, the P-order fold) carries start / stop events of its own dispatch
  * (hipExtLaunchKernelGGL), i.e. the kernel's execution time alone, with no
  * launch boundary and no event-marker latency; up to 4096 launches are
  * timed between reads.  shmemx_kernel_times waits for them and writes up to
  * max durations in microseconds to us[] and their kinds (0 fold, 1 copy,
- * 2 peers fold, 3 gather) to kind[] (may be NULL), in launch order, and the
+ * 2 peers fold, 3 gather, 4 P-order fold) to kind[] (may be NULL), in launch order, and the
  * launches past the 4096 that went untimed to *dropped (may be NULL); it
  * returns how many were written and starts over.  Off by default; timing
  * does not change what runs. */
@@ -493,7 +529,9 @@ int shmemx_mirror_stats(unsigned long long *out, int nout, int reset);
  * because a block did not reach some XCD, [9] fences checked by the SIGNAL
  * device barrier, [10] of them incomplete (the call fails); [11] one-shot
  * calls (DIRECT or SIGNAL) that ran as one fused launch, [12] two-shot calls
- * that did ($SHMEMX_FUSED_TWOSHOT_KB, default 4096).  Fills at most
+ * that did ($SHMEMX_FUSED_TWOSHOT_KB, default 4096), [13] calls that ran
+ * OWNSLICE's two-phase schedule (its phases are timed in [3]-[6]: the P-order
+ * fold as the fold, the pull of the result slots as the gather).  Fills at most
  * nout values and returns how many; reset != 0 zeroes the counters. */
 int shmemx_direct_stats(double *out, int nout, int reset);
 

@@ -25,6 +25,16 @@
 // the reference's per-PE bits on every PE.  Small arrays take the fused one
 // shot with the inputs in that order.
 //
+// Own slice (SHMEMX_ALGO_OWNSLICE, opt-in, the same six pairs above the
+// one-shot limit): own order at the two shot's traffic.  Member m folds slice
+// m from all P sources in every member's order at once (launch_fold_orders:
+// P results per element), its own result into slice m of its own target, the
+// other P - 1 into result slots in the second half of its scratch; after a
+// barrier member k copies its result of every other slice from the owners'
+// slots into its target (one gather launch).  (P-1)/P of the array in and
+// (P-1)/P out per PE, reads only, and only its owner writes a target: it
+// need not be in the heap, and exact in place needs no staging.
+//
 // Synchronisation is the reference's: a barrier before the peers' sources
 // are read (reduce-op.c:217) and one after the targets are final (:250),
 // plus one between the two phases; host barriers over the node block.  The
@@ -112,6 +122,7 @@ double g_phase_us[kNumPhases];
 double g_calls;
 double g_fused_calls;   // one-shot calls that ran as one fused launch (DIRECT and SIGNAL)
 double g_fused2_calls;  // two-shot calls that ran as one fused launch
+double g_ownslice_calls;  // calls that ran OWNSLICE's two-phase schedule
 
 double now_us() {
     return std::chrono::duration<double, std::micro>(
@@ -338,8 +349,8 @@ bool signal_args(const ActiveSet &set, SignalArgs *sa) {
 int direct_stats(double *out, int nout, bool reset) {
     // [calls, 6 phase times, host fences, host refills, device fence
     // checks, device fences that missed an XCD, fused one-shot calls, fused
-    // two-shot calls]
-    double all[1 + kNumPhases + 6] = {g_calls};
+    // two-shot calls, OWNSLICE two-phase calls]
+    double all[1 + kNumPhases + 7] = {g_calls};
     for (int i = 0; i < kNumPhases; ++i) all[1 + i] = g_phase_us[i];
     unsigned long long dev[2] = {0, 0};
     if (g_fence.dev_stats) {
@@ -352,13 +363,14 @@ int direct_stats(double *out, int nout, bool reset) {
     all[4 + kNumPhases] = (double)dev[1];
     all[5 + kNumPhases] = g_fused_calls;
     all[6 + kNumPhases] = g_fused2_calls;
+    all[7 + kNumPhases] = g_ownslice_calls;
     const int k = std::min(nout, (int)(sizeof all / sizeof all[0]));
     for (int i = 0; i < k; ++i) out[i] = all[i];
     if (reset) {
         g_calls = 0;
         for (double &v : g_phase_us) v = 0;
         g_fence.host_checks = g_fence.host_refills = 0;
-        g_fused_calls = g_fused2_calls = 0;
+        g_fused_calls = g_fused2_calls = g_ownslice_calls = 0;
         if (g_fence.dev_stats) SHMX_HIP(hipMemset(g_fence.dev_stats, 0, sizeof dev));
     }
     return k;
@@ -487,13 +499,22 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     const size_t bytes = n * sz;
     const size_t g = granule(sz);
     const size_t half = g_scratch.bytes / 2;
-    const size_t cmax = std::max(g, (half / sz) / g * g);   // elements per staged chunk
+    const bool one_shot = bytes <= oneshot_bytes();
+    // OWNSLICE above the one-shot limit: the owner of slice m folds it in
+    // every member's order (launch_fold_orders) and the members pull their
+    // results from the owners' slots in the second half of scratch.  At or
+    // below the limit the call is the own-order one shot below.
+    const bool ownslice = p.algo == SHMEMX_ALGO_OWNSLICE && !one_shot;
+    // elements per staged chunk: half the scratch; for OWNSLICE what leaves
+    // room in the other half for the P - 1 result slots of the chunk's
+    // slices (each rounded up to the granule) and their skew of < 16 bytes
+    const size_t room = ownslice ? half - std::min(half, (size_t)16 * (P + 1)) : half;
+    const size_t cmax = std::max(g, (room / sz) / g * g);
     // Small arrays: one shot — every member folds the whole array itself (in
     // set order, so all agree, or each in its own) and writes only its own
     // target: one kernel and two barriers instead of two kernels and three.
     // Same decision on every member (n is collective).  Own order is the one
     // shot's schedule at every size.
-    const bool one_shot = bytes <= oneshot_bytes();
     const bool local_write = own_order || one_shot;
 
     // Where my operands live for the peers.  A source that partially
@@ -509,7 +530,13 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     if (stage_src) d.src = node::Loc{node::kScratch, 0};
     else d.src = node::Loc{node::kHeap, off};
     bool stage_tgt;
-    if (local_write) {
+    if (ownslice) {
+        // only I write my target, a slice at a time after the phase that
+        // read it: in place needs nothing, a partial overlap has its source
+        // staged already
+        stage_tgt = false;
+        d.tgt = node::Loc{};
+    } else if (local_write) {
         stage_tgt = tgt < src + bytes && src < tgt + bytes;   // any aliasing
         d.tgt = node::Loc{};
     } else {
@@ -534,7 +561,12 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     // $SHMEMX_FUSED_TWOSHOT_KB / shmemx_set_fused_twoshot_kb), in KiB.  They
     // pick the schedule (one shot or two, fused or not) and with it the
     // number of barriers, so members that disagree on them must not start it.
-    d.aux = (uint64_t)(oneshot_bytes() >> 10) << 32 | (uint64_t)(fused_twoshot_bytes() >> 10);
+    // An OWNSLICE plan never takes the fused two shot; its chunks and result
+    // slots depend on the scratch size instead ($SHMEMX_DIRECT_SCRATCH_MB),
+    // which takes that word's place, in MiB, marked by the top bit.
+    d.aux = (uint64_t)(oneshot_bytes() >> 10) << 32 |
+            (p.algo == SHMEMX_ALGO_OWNSLICE ? 0x80000000u | (uint64_t)(g_scratch.bytes >> 20)
+                                            : (uint64_t)(fused_twoshot_bytes() >> 10));
     node::put_desc(d);
     if (single && stage_src)
         SHMX_HIP(hipMemcpyAsync(g_scratch.base, src, bytes, hipMemcpyDefault, s));
@@ -558,10 +590,16 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         read_descs();
         for (int i = 1; i < P; ++i) {
             if (desc[i].aux != desc[0].aux) {
-                trace(LOG_REDUCTION, "DIRECT: members disagree on SHMEMX_DIRECT_ONESHOT_KB / "
-                      "SHMEMX_FUSED_TWOSHOT_KB (set member %d: %llu/%llu KiB, member 0: %llu/%llu KiB)",
-                      i, (unsigned long long)(desc[i].aux >> 32), (unsigned long long)(desc[i].aux & 0xffffffffu),
-                      (unsigned long long)(desc[0].aux >> 32), (unsigned long long)(desc[0].aux & 0xffffffffu));
+                if (p.algo == SHMEMX_ALGO_OWNSLICE)
+                    trace(LOG_REDUCTION, "OWNSLICE: members disagree on SHMEMX_DIRECT_ONESHOT_KB / "
+                          "SHMEMX_DIRECT_SCRATCH_MB (set member %d: %llu KiB / %llu MiB, member 0: %llu KiB / %llu MiB)",
+                          i, (unsigned long long)(desc[i].aux >> 32), (unsigned long long)(desc[i].aux & 0x7fffffffu),
+                          (unsigned long long)(desc[0].aux >> 32), (unsigned long long)(desc[0].aux & 0x7fffffffu));
+                else
+                    trace(LOG_REDUCTION, "DIRECT: members disagree on SHMEMX_DIRECT_ONESHOT_KB / "
+                          "SHMEMX_FUSED_TWOSHOT_KB (set member %d: %llu/%llu KiB, member 0: %llu/%llu KiB)",
+                          i, (unsigned long long)(desc[i].aux >> 32), (unsigned long long)(desc[i].aux & 0xffffffffu),
+                          (unsigned long long)(desc[0].aux >> 32), (unsigned long long)(desc[0].aux & 0xffffffffu));
                 // nobody reads anyone's operands: the call ends here on every
                 // member, after one more barrier, so that no member's next
                 // call overwrites its descriptor before a slower member has
@@ -589,7 +627,18 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         chunked |= (desc[i].count & 1) != 0;
         backwards |= (desc[i].count & 2) != 0;
     }
-    if (!map_members(desc, local_write, set)) {
+    bool mapped;
+    if (ownslice) {   // every member's source and its result slots
+        std::vector<std::pair<node::Region, int>> regs;
+        for (int i = 0; i < P; ++i) {
+            regs.emplace_back(static_cast<node::Region>(desc[i].src.region), set.pe_of(i));
+            regs.emplace_back(node::kScratch, set.pe_of(i));
+        }
+        mapped = map_regions(regs, set);
+    } else {
+        mapped = map_members(desc, local_write, set);
+    }
+    if (!mapped) {
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer region (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
@@ -600,6 +649,12 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         if (!local_write)
             tbase[i] = node::peer_base(static_cast<node::Region>(desc[i].tgt.region), set.pe_of(i)) +
                        desc[i].tgt.off;
+    }
+    if (ownslice) {
+        // the result slots of a chunk must fit the second half of scratch
+        // whether or not anybody stages (n is collective)
+        chunked |= !single;
+        g_ownslice_calls += 1;
     }
     const size_t C = chunked ? cmax : std::max<size_t>(n, 1);
     const size_t nchunks = (n + C - 1) / C;
@@ -620,6 +675,39 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         auto at = [&](char *base, const node::Loc &l, size_t elem) {
             return base + (l.region == node::kScratch ? elem - c0 : elem) * sz;
         };
+        if (ownslice) {
+            // slice i of the chunk belongs to member i; every owner's slots
+            // start at the same offset mod 16 as the sources (member 0's
+            // stands for all: a symmetric source has one offset), so the
+            // fold's 2 P arrays share an alignment whenever the target does
+            const Slices sl(cnt, P, sz);
+            const size_t lo = sl.lo(m), hi = sl.hi(m);
+            const size_t skew = desc[0].src.region == node::kScratch ? 0 : desc[0].src.off & 15u;
+            auto slots_of = [&](int i) { return node::peer_base(node::kScratch, set.pe_of(i)) + half + skew; };
+            // 1. my slice of every member's source, in every member's order:
+            // mine into my target, the others into my slots
+            const double tf = now_us();
+            if (hi > lo) {
+                void *outs[kMaxFoldInputs];
+                for (int i = 0; i < P; ++i) {
+                    ins[i] = at(sbase[i], desc[i].src, c0 + lo);
+                    outs[i] = i == m ? tgt + (c0 + lo) * sz : scratch_tgt + skew + order_slot(sl, m, i);
+                }
+                SHMX_HIP(launch_fold_orders(type, op, outs, ins.data(), P, hi - lo, s));
+            }
+            // every owner's slots are final
+            node_sync(start, step, P, s, &g_phase_us[kFold], &g_phase_us[kFoldBarrier], tf);
+            // 2. my result of every other slice, from its owner's slots
+            const void *from[kMaxFoldInputs];
+            void *to[kMaxFoldInputs];
+            size_t len[kMaxFoldInputs];
+            const int nseg = gather_order_slots(sl, m, slots_of, tgt + c0 * sz, from, to, len);
+            const double tg = now_us();
+            SHMX_HIP(launch_gather(from, to, len, nseg, s));
+            // reduce-op.c:250: no member reads my source or my slots any more
+            node_done(start, step, P, s, &g_phase_us[kGather], &g_phase_us[kExitBarrier], tg);
+            continue;
+        }
         if (local_write) {
             // own order: src_me first, then the others ascending
             // (reduce-op.c:219-248); one shot: set order

@@ -40,14 +40,14 @@ namespace shmx {
 
 // ------------------------------------------------------------ kernel clock
 // shmemx_kernel_timing(1): the fold-family launches (2-input and P-input
-// folds, the copy, the peers fold, the gather) go through
+// folds, the copy, the peers fold, the gather, the P-order fold) go through
 // hipExtLaunchKernelGGL with a start / stop event pair: the dispatch's own
 // timestamps, i.e. the kernel alone, with no launch boundary and no
 // event-marker latency (a marker pair around a 9 us fold reads 14.7 us,
 // rocprofv3 8.6, profiles/r04_midsize.txt).  shmemx_kernel_times() hands
 // the durations back in launch order.  Off (the default), the launches are
 // plain hipLaunchKernelGGL.
-enum KernelKind { kKindFold = 0, kKindCopy = 1, kKindPeers = 2, kKindGather = 3 };
+enum KernelKind { kKindFold = 0, kKindCopy = 1, kKindPeers = 2, kKindGather = 3, kKindOrders = 4 };
 namespace {
 constexpr size_t kClockPairs = 4096;
 struct KClock {
@@ -355,6 +355,116 @@ __global__ __launch_bounds__(kBlock) void fold_peers_kernel(FoldArgs args) {
                 st16<NT>(out + v, acc);
             }
         }
+    }
+}
+
+// The P-order fold (OWNSLICE's reduce phase, shmemx_fold_orders_on_stream):
+// nins inputs, nins outputs,
+//     outs[k][i] = ap(...ap(ap(ins[k][i], ins[j0][i]), ins[j1][i])...),
+// j ascending over the other inputs: member k's own reference order
+// (reduce-op.c:219-248; set_geom.h fold_inputs with own_order) for every k at
+// once, for the min / max pairs whose a<b?a:b is not associative under NaN
+// and signed zeros (own_order_pair).  The owner of a slice has all P inputs
+// of an element in registers anyway, so it emits all P answers from one read.
+//
+// Loads as in fold_peers_kernel: every lane issues its vectors of ALL
+// inputs before folding any, so every peer link carries loads at once, and
+// before storing any output, so outs[k] may be ins[k] (the in-place call).
+// Same head / 16-byte body / tail split; every vector is guarded.
+//
+// U (vectors per input per lane) and registers.  The peers fold keeps
+// MAXIN x U = 32 vectors in registers and one accumulator.  Here all P
+// orders of a vector are independent chains, which the scheduler interleaves,
+// so the accumulators and compare results of up to 16 orders live beside the
+// inputs.  hipcc (ROCm 7), gfx950, -O3, VGPRs + AGPRs / scratch bytes per
+// lane / waves per SIMD, float and double alike:
+//     MAXIN 8    U = 4  254 + 76 / 0 / 1    U = 2  195 / 0 / 2    U = 1   77 / 0 / 6
+//     MAXIN 16   U = 2  256 + 120 / 0 / 1                         U = 1  142 / 0 / 3
+// (capping the registers for 4 waves, amdgpu_waves_per_eu, spills: 52-268
+// bytes).  U = 1 everywhere: 6 waves x 8 loads or 3 waves x 16 in flight per
+// SIMD, more than U = 2 gives at its occupancy, and nothing spills.  With
+// U = 1 a chunk is one vector per lane, so the guarded path is the only
+// vector path: within a vector the loads of all inputs are issued back to
+// back under one wave-uniform guard, with no wait between them.
+// float and double unroll both loops (k over the orders, j over the
+// inputs): P(P-1) selects per element of straight-line code, 240 at P = 16.
+// long double's compare is ~40 instructions of software x87, which unrolled
+// P^2 times would be far past the instruction cache: it takes a ROLLED loop
+// over the orders, whose first input is picked by a chain of uniform selects
+// (x[k] with a run-time k would put the inputs in scratch): 82 VGPRs at
+// MAXIN 8, 148 at 16, no scratch.
+constexpr int kUnrollOrders = 1;
+
+struct OrdersArgs {
+    void *outs[kMaxFoldInputs];
+    const void *ins[kMaxFoldInputs];
+    int nins;
+    size_t head, nvec, tail;   // as FoldArgs
+};
+
+// member k's order over the values x[0..nins): x[k], then the others ascending
+template <typename T, int OP, int MAXIN, bool ROLLED, typename V, typename Ap, typename St>
+__device__ __forceinline__ void fold_orders_of(const V (&x)[MAXIN], int nins, Ap ap, St store) {
+    if constexpr (ROLLED) {
+#pragma unroll 1
+        for (int k = 0; k < nins; ++k) {
+            V acc = x[0];
+#pragma unroll
+            for (int j = 1; j < MAXIN; ++j)
+                if (j == k) acc = x[j];
+#pragma unroll
+            for (int j = 0; j < MAXIN; ++j)
+                if (j != k && j < nins) acc = ap(acc, x[j]);
+            store(k, acc);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXIN; ++k) {
+            if (k < nins) {
+                V acc = x[k];
+#pragma unroll
+                for (int j = 0; j < MAXIN; ++j)
+                    if (j != k && j < nins) acc = ap(acc, x[j]);
+                store(k, acc);
+            }
+        }
+    }
+}
+
+template <typename T, int OP, int MAXIN, int NT>
+__global__ __launch_bounds__(kBlock) void fold_orders_kernel(OrdersArgs args) {
+    constexpr int E = 16 / sizeof(T);
+    constexpr bool ROLLED = std::is_same<T, ld80>::value;
+    const int nins = args.nins;
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const size_t nthr = (size_t)gridDim.x * kBlock;
+    {
+        const size_t body_end = args.head + args.nvec * E;
+        const size_t nscalar = args.head + args.tail;
+        for (size_t s = tid; s < nscalar; s += nthr) {
+            const size_t i = s < args.head ? s : body_end + (s - args.head);
+            T x[MAXIN];
+#pragma unroll
+            for (int k = 0; k < MAXIN; ++k)
+                if (k < nins) x[k] = static_cast<const T *>(args.ins[k])[i];
+            fold_orders_of<T, OP, MAXIN, ROLLED>(
+                x, nins, [](T a, T b) { return Op<T, OP>::ap(a, b); },
+                [&](int k, T r) { static_cast<T *>(args.outs[k])[i] = r; });
+        }
+    }
+    if (args.nvec == 0) return;
+    auto in = [&](int k) {
+        return reinterpret_cast<const u32x4 *>(static_cast<const T *>(args.ins[k]) + args.head);
+    };
+    auto out = [&](int k) { return reinterpret_cast<u32x4 *>(static_cast<T *>(args.outs[k]) + args.head); };
+    auto ap16 = [](u32x4 a, u32x4 b) { return apply16<T, OP>(a, b); };
+    const size_t nvec = args.nvec;
+    for (size_t v = tid; v < nvec; v += nthr) {
+        u32x4 x[MAXIN];
+#pragma unroll
+        for (int k = 0; k < MAXIN; ++k)
+            if (k < nins) x[k] = ld16<NT>(in(k) + v);
+        fold_orders_of<T, OP, MAXIN, ROLLED>(x, nins, ap16, [&](int k, u32x4 r) { st16<NT>(out(k) + v, r); });
     }
 }
 
@@ -701,6 +811,77 @@ hipError_t launch_fold_peers(int type, int op, void *out, const void *const *ins
         ptrs[k + 1] = ins[k];
     }
     return dispatch(type, op, a, ptrs, nins + 1, n, stream);
+}
+
+// ------------------------------------------------------- the P-order fold
+namespace {
+
+template <typename T, int OP, int MAXIN, int NT>
+void launch_orders_grid(const OrdersArgs &a, hipStream_t stream) {
+    FoldArgs g{};
+    g.head = a.head;
+    g.nvec = a.nvec;
+    g.tail = a.tail;
+    launch_k(kKindOrders, fold_orders_kernel<T, OP, MAXIN, NT>,
+             dim3((unsigned)grid_for(g, kUnrollOrders)), dim3(kBlock), stream, a);
+}
+
+// P reads and P writes of n elements: non-temporal from 32 MiB moved, as the
+// other folds (kNtThresholdBytes)
+template <typename T, int OP>
+hipError_t launch_orders_typed(const OrdersArgs &a, size_t n, hipStream_t stream) {
+    const bool nt = (size_t)(2 * a.nins) * n * sizeof(T) >= kNtThresholdBytes;
+    if (a.nins <= 8) {
+        if (nt) launch_orders_grid<T, OP, 8, 3>(a, stream);
+        else launch_orders_grid<T, OP, 8, 0>(a, stream);
+    } else {
+        if (nt) launch_orders_grid<T, OP, 16, 3>(a, stream);
+        else launch_orders_grid<T, OP, 16, 0>(a, stream);
+    }
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_orders_ops(int op, const OrdersArgs &a, size_t n, hipStream_t stream) {
+    return op == SHMEMX_OP_MIN ? launch_orders_typed<T, SHMEMX_OP_MIN>(a, n, stream)
+                               : launch_orders_typed<T, SHMEMX_OP_MAX>(a, n, stream);
+}
+
+}  // namespace
+
+hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
+                              hipStream_t stream) {
+    if ((op != SHMEMX_OP_MIN && op != SHMEMX_OP_MAX) || nins < 1 || nins > kMaxFoldInputs || !outs || !ins)
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const size_t sz = type_size(type);
+    OrdersArgs a{};
+    a.nins = nins;
+    // the vector body only if all 2 P arrays share one offset mod 16 that is
+    // a whole number of elements (dispatch's rule)
+    const uintptr_t off = reinterpret_cast<uintptr_t>(ins[0]) & 15u;
+    bool same = sz && (off % sz) == 0;
+    for (int k = 0; k < nins; ++k) {
+        if (!ins[k] || !outs[k]) return hipErrorInvalidValue;
+        a.ins[k] = ins[k];
+        a.outs[k] = outs[k];
+        same = same && (reinterpret_cast<uintptr_t>(ins[k]) & 15u) == off &&
+               (reinterpret_cast<uintptr_t>(outs[k]) & 15u) == off;
+    }
+    if (same) {
+        const size_t E = 16 / sz;
+        a.head = std::min(n, ((16 - off) & 15u) / sz);
+        a.nvec = (n - a.head) / E;
+        a.tail = n - a.head - a.nvec * E;
+    } else {
+        a.head = n;
+    }
+    switch (type) {
+    case SHMEMX_TYPE_FLOAT: return launch_orders_ops<float>(op, a, n, stream);
+    case SHMEMX_TYPE_DOUBLE: return launch_orders_ops<double>(op, a, n, stream);
+    case SHMEMX_TYPE_LONGDOUBLE: return launch_orders_ops<ld80>(op, a, n, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // ------------------------------------------------------------ gather copy

@@ -69,6 +69,12 @@ hipError_t launch_host_signal(const HostSignal &sig, hipStream_t stream);
 hipError_t launch_fold_peers(int type, int op, void *out, const void *const *ins, int nins, size_t n,
                              hipStream_t stream);
 
+// The P-order fold: outs[k] = ins[k] folded with the other inputs ascending,
+// for every k in one pass (each member's own reference order; float, double
+// and long double min / max only).  outs[k] may be ins[k]; no other overlap.
+hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
+                              hipStream_t stream);
+
 // Copy nseg (<= kMaxFoldInputs) byte ranges srcs[i] -> dsts[i] in one launch
 // (DIRECT all-gather: the peers' result slices, read concurrently).
 hipError_t launch_gather(const void *const *srcs, void *const *dsts, const size_t *bytes, int nseg,

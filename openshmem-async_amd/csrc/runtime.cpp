@@ -176,6 +176,7 @@ static int parse_algo(const char *s) {
     if (v == "allreduce") return SHMEMX_ALGO_ALLREDUCE;
     if (v == "direct") return SHMEMX_ALGO_DIRECT;
     if (v == "signal") return SHMEMX_ALGO_SIGNAL;
+    if (v == "ownslice") return SHMEMX_ALGO_OWNSLICE;
     return SHMEMX_ALGO_AUTO;
 }
 
@@ -421,7 +422,9 @@ static bool rccl_native(int type, int op) {
 // hands every member one shared result can give that, so for these pairs
 // every algorithm folds in the calling PE's own order: every member reads
 // every member's whole source ((P-1)·S per PE, against 2(P-1)/P·S for a
-// shared result).
+// shared result).  SHMEMX_ALGO_OWNSLICE gets the shared
+// result's traffic without sharing a result: the owner of a slice folds it in
+// every member's order and each member pulls its own (direct.cpp).
 bool own_order_pair(int type, int op) {
     return (op == SHMEMX_OP_MIN || op == SHMEMX_OP_MAX) &&
            (type == SHMEMX_TYPE_FLOAT || type == SHMEMX_TYPE_DOUBLE || type == SHMEMX_TYPE_LONGDOUBLE);
@@ -449,7 +452,9 @@ static long long allreduce_max_bytes() {
 // $SHMEMX_AUTO_PARTIAL for partial and strided sets, each a list of
 // "bytes:algo" cut points in ascending order ("0:allreduce,3145728:rccl":
 // arrays of fewer than 3 MiB per PE take one all-reduce, larger ones
-// reduce-scatter + all-gather).  Names: allreduce, rccl, a2a, direct, gather.
+// reduce-scatter + all-gather).  Names: allreduce, rccl, a2a, direct, gather,
+// ownslice (which applies where a direct cut would, to the six own-order
+// pairs only).
 // A cut whose algorithm cannot serve a call (an RCCL algorithm for a pair
 // RCCL does not reduce as the reference does, DIRECT without the node block)
 // falls back to the built-in rule, so every PE still plans alike.  Unset or
@@ -475,7 +480,7 @@ static std::vector<AutoCut> parse_auto_table(const char *var) {
         const std::string name = colon == std::string::npos ? "" : item.substr(colon + 1);
         const int a = parse_algo(name.c_str());
         const bool named = name == "allreduce" || name == "rccl" || name == "a2a" || name == "direct" ||
-                           name == "gather";
+                           name == "gather" || name == "ownslice";
         if (b < 0 || stop != item.c_str() + colon || !named || b <= last) {
             trace(LOG_INFO, "%s=\"%s\": unusable cut \"%s\"; the built-in rule applies", var, e,
                   item.c_str());
@@ -530,10 +535,13 @@ int make_plan(int type, int op, int nreduce, int start, int logstride, int size,
         const bool pull_ok = g_state.node_shared && P <= kMaxFoldInputs && !cap.auto_algo;
         if (((t == SHMEMX_ALGO_RCCL || t == SHMEMX_ALGO_ALLREDUCE) && rccl_ok) ||
             (t == SHMEMX_ALGO_A2A && !g_state.ipc_only && !own) || (t == SHMEMX_ALGO_DIRECT && pull_ok) ||
-            t == SHMEMX_ALGO_GATHER)
+            (t == SHMEMX_ALGO_OWNSLICE && pull_ok && own) || t == SHMEMX_ALGO_GATHER)
             algo = t;
     }
     if (algo == SHMEMX_ALGO_AUTO && own) algo = SHMEMX_ALGO_GATHER;
+    // OWNSLICE is the six pairs' two shot; everything else it is asked for
+    // is DIRECT's, so the job may set it for every call
+    if (algo == SHMEMX_ALGO_OWNSLICE && !own) algo = SHMEMX_ALGO_DIRECT;
     // A2A's owner hands one result to every member: for these pairs its
     // exchange is GATHER's
     if (algo == SHMEMX_ALGO_A2A && own) algo = SHMEMX_ALGO_GATHER;
@@ -554,9 +562,10 @@ int make_plan(int type, int op, int nreduce, int start, int logstride, int size,
     if ((algo == SHMEMX_ALGO_RCCL || algo == SHMEMX_ALGO_ALLREDUCE) && !(set_rccl && rccl_native(type, op)))
         return SHMEMX_ENOTSUP;
     if (g_state.ipc_only && algo != SHMEMX_ALGO_DIRECT && algo != SHMEMX_ALGO_GATHER &&
-        algo != SHMEMX_ALGO_SIGNAL)
+        algo != SHMEMX_ALGO_SIGNAL && algo != SHMEMX_ALGO_OWNSLICE)
         return SHMEMX_ENOTSUP;   // no RCCL communicator on the IPC transport
-    if ((algo == SHMEMX_ALGO_DIRECT || algo == SHMEMX_ALGO_SIGNAL) && size > kMaxFoldInputs)
+    if ((algo == SHMEMX_ALGO_DIRECT || algo == SHMEMX_ALGO_SIGNAL || algo == SHMEMX_ALGO_OWNSLICE) &&
+        size > kMaxFoldInputs)
         return SHMEMX_ENOTSUP;
     p->algo = algo;
     p->member = m;
@@ -583,6 +592,17 @@ int make_plan(int type, int op, int nreduce, int start, int logstride, int size,
     case SHMEMX_ALGO_DIRECT:
     case SHMEMX_ALGO_SIGNAL:   // slice per member (own order: all of it); no workspace
         p->chunk = own ? n : (long long)Slices(n, P, sz).slice;
+        break;
+    case SHMEMX_ALGO_OWNSLICE:
+        // above the one-shot limit a slice per member and P - 1 result slots
+        // of one slice each in the IPC scratch region; up to it, DIRECT's
+        // own-order one shot
+        if ((size_t)(n * sz) > oneshot_bytes()) {
+            p->chunk = (long long)Slices(n, P, sz).slice;
+            p->ws_bytes = (long long)(P - 1) * p->chunk * sz;
+        } else {
+            p->chunk = n;
+        }
         break;
     default:  // GATHER (IPC transport: read in place, no workspace)
         p->chunk = n;
@@ -708,7 +728,10 @@ int reduce_device(int type, int op, void *target, const void *source,
     }
     if (collective && pulls_over_ipc(p)) {
         const bool own_order = p.algo == SHMEMX_ALGO_GATHER || own;
-        if (log_enabled(LOG_REDUCTION))
+        if (log_enabled(LOG_REDUCTION) && p.algo == SHMEMX_ALGO_OWNSLICE)
+            trace(LOG_REDUCTION, "type %d op %d nreduce %d set (%d,%d,%d) member %d algo ownslice chunk %lld",
+                  type, op, nreduce, start, logstride, size, p.member, p.chunk);
+        else if (log_enabled(LOG_REDUCTION))
             trace(LOG_REDUCTION, "type %d op %d nreduce %d set (%d,%d,%d) member %d algo %s%s",
                   type, op, nreduce, start, logstride, size, p.member,
                   p.algo == SHMEMX_ALGO_DIRECT ? "direct" : "gather (ipc)", own_order ? " (own order)" : "");
@@ -723,7 +746,7 @@ int reduce_device(int type, int op, void *target, const void *source,
 
     if (log_enabled(LOG_REDUCTION)) {
         static const char *const algos[SHMEMX_NALGOS] = {"auto", "rccl", "a2a", "gather",
-                                                         "allreduce", "direct", "signal"};
+                                                         "allreduce", "direct", "signal", "ownslice"};
         trace(LOG_REDUCTION, "type %d op %d nreduce %d set (%d,%d,%d) member %d algo %s chunk %lld",
               type, op, nreduce, start, logstride, size, p.member, algos[p.algo], p.chunk);
     }
@@ -1164,6 +1187,31 @@ int shmemx_fold_n_on_stream(int type, int op, void *out, const void *const *ins,
 int shmemx_fold_n_peers_on_stream(int type, int op, void *out, const void *const *ins,
                                   int nins, size_t nelems, void *stream) {
     return fold_n(type, op, out, ins, nins, nelems, stream, true);
+}
+
+int shmemx_fold_orders_on_stream(int type, int op, void *const *outs, const void *const *ins, int nins,
+                                 size_t nelems, void *stream) {
+    t_last_error = SHMEMX_OK;
+    if (!op_valid(type, op) || nins < 1 || nins > kMaxFoldInputs) return set_error(SHMEMX_EINVAL);
+    if (!own_order_pair(type, op)) return set_error(SHMEMX_ENOTSUP);
+    if (nelems == 0) return SHMEMX_OK;
+    if (!outs || !ins) return set_error(SHMEMX_EINVAL);
+    const size_t bytes = nelems * type_size(type);
+    auto meet = [bytes](const void *a, const void *b) {
+        const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
+        return x < y + bytes && y < x + bytes;
+    };
+    for (int k = 0; k < nins; ++k)
+        if (!outs[k] || !ins[k]) return set_error(SHMEMX_EINVAL);
+    // an output may be its own input (exactly), and nothing else
+    for (int k = 0; k < nins; ++k)
+        for (int j = 0; j < nins; ++j)
+            if ((j != k && (meet(outs[k], ins[j]) || meet(outs[k], outs[j]))) || overlap(outs[k], ins[k], bytes))
+                return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    if (launch_fold_orders(type, op, outs, ins, nins, nelems, static_cast<hipStream_t>(stream)) != hipSuccess)
+        return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
 }
 
 int shmemx_gather_on_stream(const void *const *srcs, void *const *dsts, const size_t *bytes,

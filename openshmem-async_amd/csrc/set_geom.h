@@ -76,4 +76,32 @@ inline int gather_segments(const Slices &sl, int m, bool rotated, bool include_m
     return k;
 }
 
+// OWNSLICE: the owner of a slice folds it once per member order and keeps
+// the P - 1 results that are not its own in consecutive slots of sl.slice
+// elements each, in member order with its own index left out.  The byte
+// offset of member k's result in owner's slot area (k != owner); the area is
+// order_slots_bytes(sl) long.
+inline size_t order_slot(const Slices &sl, int owner, int k) {
+    return (size_t)(k < owner ? k : k - 1) * sl.slice * sl.elem_size;
+}
+inline size_t order_slots_bytes(const Slices &sl) { return (size_t)(sl.P - 1) * sl.slice * sl.elem_size; }
+
+// The segments member m gathers in OWNSLICE's second phase: from every other
+// owner i of a non-empty slice, m's result slot in i's slot area at
+// slots_of(i), to slice i of tgt; from member m + 1 on, wrapping, as the
+// rotated gather above.  Returns how many (room for P - 1 each).
+template <class SlotsOf>
+inline int gather_order_slots(const Slices &sl, int m, SlotsOf slots_of, char *tgt, const void **from,
+                              void **to, size_t *len) {
+    int k = 0;
+    for (int r = 0; r + 1 < sl.P; ++r) {
+        const int i = (m + 1 + r) % sl.P;
+        if (sl.count(i) == 0) continue;
+        from[k] = slots_of(i) + order_slot(sl, i, m);
+        to[k] = tgt + sl.lo(i) * sl.elem_size;
+        len[k++] = sl.count(i) * sl.elem_size;
+    }
+    return k;
+}
+
 }  // namespace shmx

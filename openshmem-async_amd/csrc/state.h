@@ -224,9 +224,10 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
 void direct_release();
 // This plan pulls over IPC mappings and returns with its work done (host
 // barriers, or the fused launch's host signal): DIRECT, and own-order GATHER
-// on the IPC transport.
+// on the IPC transport, OWNSLICE.
 inline bool pulls_over_ipc(const shmemx_plan_t &p) {
-    return p.algo == SHMEMX_ALGO_DIRECT || (p.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only);
+    return p.algo == SHMEMX_ALGO_DIRECT || p.algo == SHMEMX_ALGO_OWNSLICE ||
+           (p.algo == SHMEMX_ALGO_GATHER && g_state.ipc_only);
 }
 // Arrays up to this size take DIRECT's and SIGNAL's one shot
 // ($SHMEMX_DIRECT_ONESHOT_KB, default 256 KiB; every PE must agree).

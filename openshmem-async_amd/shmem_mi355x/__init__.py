@@ -25,7 +25,7 @@ TYPES = {"short": 0, "int": 1, "long": 2, "longlong": 3, "float": 4,
          "double": 5, "longdouble": 6, "complexd": 7, "complexf": 8}
 OPS = {"sum": 0, "prod": 1, "and": 2, "or": 3, "xor": 4, "min": 5, "max": 6}
 ALGOS = {"auto": 0, "rccl": 1, "a2a": 2, "gather": 3, "allreduce": 4, "direct": 5,
-         "signal": 6}
+         "signal": 6, "ownslice": 7}
 ERRORS = {0: "OK", 1: "EINVAL", 2: "ENOTMEMBER", 3: "ENOTSUP", 4: "ENOINIT",
           5: "ENOMEM", 6: "EDEVICE"}
 
@@ -111,6 +111,8 @@ def lib() -> ctypes.CDLL:
     L.shmemx_fold_n_on_stream.restype = i
     L.shmemx_fold_n_peers_on_stream.argtypes = [i, i, vp, ctypes.POINTER(vp), i, sz, vp]
     L.shmemx_fold_n_peers_on_stream.restype = i
+    L.shmemx_fold_orders_on_stream.argtypes = [i, i, ctypes.POINTER(vp), ctypes.POINTER(vp), i, sz, vp]
+    L.shmemx_fold_orders_on_stream.restype = i
     L.shmemx_gather_on_stream.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp),
                                           ctypes.POINTER(sz), i, vp]
     L.shmemx_gather_on_stream.restype = i
@@ -321,6 +323,18 @@ def fold_n(type_name: str, op: str, out, ins, nelems: int, stream: int = 0, peer
     _check(rc, f"shmemx_fold_n{'_peers' if peers else ''}_on_stream({type_name},{op})")
 
 
+def fold_orders_on_stream(type_name: str, op: str, outs, ins, nelems: int, stream: int = 0) -> None:
+    """shmemx_fold_orders_on_stream: outs[k] = ins[k] folded with the other
+    inputs ascending, for every k in one launch (each member's own reference
+    order; float / double / longdouble min and max).  outs[k] may be ins[k]."""
+    if len(outs) != len(ins):
+        raise ValueError("one output per input")
+    a = (ctypes.c_void_p * len(outs))(*[addr(x) for x in outs])
+    b = (ctypes.c_void_p * len(ins))(*[addr(x) for x in ins])
+    rc = lib().shmemx_fold_orders_on_stream(TYPES[type_name], OPS[op], a, b, len(ins), nelems, stream or None)
+    _check(rc, f"shmemx_fold_orders_on_stream({type_name},{op})")
+
+
 def gather(srcs, dsts, nbytes, stream: int = 0) -> None:
     """shmemx_gather_on_stream: copy byte ranges srcs[i] -> dsts[i] in one
     launch (DIRECT's all-gather kernel)."""
@@ -384,7 +398,7 @@ def set_comms() -> int:
     return lib().shmemx_set_comms()
 
 
-KERNEL_KINDS = ("fold", "copy", "peers_fold", "gather")
+KERNEL_KINDS = ("fold", "copy", "peers_fold", "gather", "orders_fold")
 
 
 def kernel_timing(on: bool) -> None:
@@ -450,7 +464,7 @@ DIRECT_PHASES = ("entry_wait_us", "entry_barrier_us", "fold_us", "fold_barrier_u
 
 
 FENCE_STATS = ("fences_host", "fence_refills_host", "fences_device", "fences_device_incomplete")
-DIRECT_COUNTS = ("fused_calls", "fused_twoshot_calls")
+DIRECT_COUNTS = ("fused_calls", "fused_twoshot_calls", "ownslice_calls")
 
 
 def direct_stats(reset: bool = True) -> dict:
@@ -458,7 +472,8 @@ def direct_stats(reset: bool = True) -> dict:
     microseconds summed over them per phase, and the system-fence coverage
     counters (fences checked on the host / refilled because a fence missed an
     XCD; fences checked by the SIGNAL barrier / found incomplete), and the
-    one-shot calls that ran as one fused launch."""
+    one-shot / two-shot calls that ran as one fused launch and the calls that
+    ran OWNSLICE's two-phase schedule."""
     names = DIRECT_PHASES + FENCE_STATS + DIRECT_COUNTS
     buf = (ctypes.c_double * (1 + len(names)))()
     k = lib().shmemx_direct_stats(buf, len(buf), 1 if reset else 0)
