@@ -434,6 +434,38 @@ int shmemx_rccl_register_heap(int on);
  * written. */
 int shmemx_service_stats(unsigned long long *out, int nout, int reset);
 
+/* Test hook: one fold request of the small-call exchange, in one process.
+ * The set is (PE_start, logPE_stride, PE_size) among PEs 0..63 and the caller
+ * plays PE `me`, a member.  srcs[i] is a host array of nelems elements, the
+ * source of member PE_start + (i << logPE_stride).  The hook keeps a private
+ * image of the exchange's 64 slots (page-locked, device-mapped, 4 KiB-aligned;
+ * made on first use, freed at shmem_finalize), fills every byte of all 64
+ * slots with 0xA5, copies each srcs[i] to the start of its member's slot, and
+ * posts one fold request to the resident service workgroup, exactly as a
+ * small multi-PE blocking call does after its entry barrier: the workgroup
+ * folds the members' slots in PE_start's order, or with own_order != 0 in
+ * me's own order (me first, then the others ascending), into dst and, if not
+ * NULL, dst2 as well.  dst and dst2 are device-accessible addresses of the
+ * caller's (device memory or page-locked host memory) with any element
+ * alignment.  Blocking; the request counts in shmemx_service_stats as served
+ * and as a fold.
+ * What is real: the kernel, the mailbox request and its cfg word, the loads of
+ * the slots and the stores to the targets.  What is not: the image comes from
+ * hipHostMalloc, while the job's exchange is POSIX shared memory page-locked
+ * with hipHostRegister, so the hook shows nothing about that mapping kind nor
+ * about one GPU seeing what another PE's CPU or GPU wrote into a slot.
+ * Returns EINVAL, before any HIP call, for a pair the reference lacks,
+ * PE_size outside 1..64, PE_start < 0, logPE_stride outside 0..7, a last
+ * member at 64 or above, me not a member, nelems elements larger than one
+ * slot (4 KiB), NULL dst, or, with nelems > 0, NULL srcs or a NULL entry;
+ * else OK at once for nelems == 0; else ENOTSUP without shmem_init or with
+ * the service off ($SHMEMX_SERVICE=0, or PE processes sharing the GPU);
+ * EDEVICE if the mailbox or the image cannot be had. */
+int shmemx_service_fold_loopback(int type, int op, int own_order,
+                                 int PE_start, int logPE_stride, int PE_size, int me,
+                                 void *dst, void *dst2,
+                                 const void *const *srcs, size_t nelems);
+
 int shmemx_kernel_timing(int on);
 int shmemx_kernel_times(double *us, int *kind, int max, unsigned long long *dropped);
 

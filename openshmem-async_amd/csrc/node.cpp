@@ -160,11 +160,28 @@ void xchg_detach() {
     munmap(g_node.xchg, kXchgBytes);
     g_node.xchg = g_node.xchg_dev = nullptr;
 }
+// The mapped block page-locked and mapped into the GPU's address space: the
+// service workgroups of every member read and write it over PCIe.  On failure
+// the block is unmapped again.
+bool xchg_page_lock() {
+    void *d = nullptr;
+    if (hipHostRegister(g_node.xchg, kXchgBytes, hipHostRegisterMapped) != hipSuccess ||
+        hipHostGetDevicePointer(&d, g_node.xchg, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        trace(LOG_INIT, "small-call exchange %s: page-locking failed", g_node.xname.c_str());
+        xchg_detach();
+        return false;
+    }
+    g_node.xchg_dev = static_cast<char *>(d);
+    trace(LOG_INIT, "small-call exchange %s: device %p", g_node.xname.c_str(), d);
+    return true;
+}
 }  // namespace
 
-bool xchg_attach() {
-    if (g_node.xchg_dev) return true;
+bool xchg_attach(bool page_lock) {
+    if (g_node.xchg_dev || (g_node.xchg && !page_lock)) return true;
     if (!g_node.sh) return false;
+    if (g_node.xchg) return xchg_page_lock();
     char name[64];
     snprintf(name, sizeof name, "/shmemx_xchg_%016llx", (unsigned long long)g_node.hash);
     const int fd = shm_open(name, O_RDWR | O_CREAT, 0600);
@@ -178,23 +195,12 @@ bool xchg_attach() {
     close(fd);
     if (p == MAP_FAILED) return false;
     g_node.xchg = static_cast<char *>(p);
-    // page-locked and mapped into the GPU's address space: the service
-    // workgroups of every member read and write it over PCIe
-    void *d = nullptr;
-    if (hipHostRegister(p, kXchgBytes, hipHostRegisterMapped) != hipSuccess ||
-        hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        trace(LOG_INIT, "small-call exchange %s: page-locking failed", name);
-        xchg_detach();
-        return false;
-    }
-    g_node.xchg_dev = static_cast<char *>(d);
-    trace(LOG_INIT, "small-call exchange %s (%zu bytes) at %p, device %p", name, kXchgBytes, p, d);
-    return true;
+    trace(LOG_INIT, "small-call exchange %s (%zu bytes) at %p", name, kXchgBytes, p);
+    return !page_lock || xchg_page_lock();
 }
 
 char *xchg_host(int q) {
-    return g_node.xchg_dev && q >= 0 && q < kMaxPes ? g_node.xchg + (size_t)q * kXchgSlotBytes : nullptr;
+    return g_node.xchg && q >= 0 && q < kMaxPes ? g_node.xchg + (size_t)q * kXchgSlotBytes : nullptr;
 }
 
 char *xchg_dev(int q) {

@@ -80,11 +80,13 @@ bool agree(int start, int step, int P, bool ok);
 // side, at the start of its next call; normally at once), so a call needs no
 // exit barrier.  xchg_attach maps and registers the block (false on any
 // error; every PE calls it at init and the job agrees); the name goes with
-// unlink_name().
+// unlink_name().  With page_lock false it only maps the block: xchg_host,
+// xchg_claim and xchg_finish, the host side of the protocol, then work with
+// no GPU (tests/native/test_xchg.cpp), and xchg_dev stays null.
 constexpr size_t kXchgSlotBytes = 4096;
-bool xchg_attach();
-char *xchg_host(int pe);   // a slot's host address (nullptr if not attached)
-char *xchg_dev(int pe);    // the same slot's device address
+bool xchg_attach(bool page_lock = true);
+char *xchg_host(int pe);   // a slot's host address (nullptr if not mapped)
+char *xchg_dev(int pe);    // the same slot's device address (nullptr if not page-locked)
 // Start this PE's part of a call over the members start + i * step, i < P:
 // wait until the readers of its previous call are done with its slot, and
 // count the call with every other member (counts[i] for member i).

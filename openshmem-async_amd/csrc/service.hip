@@ -350,6 +350,10 @@ struct Service {
     // nanoseconds summed over the served calls: from entering service_copy
     // to the post, and from the post to seeing the result done
     unsigned long long ns_before_post = 0, ns_round_trip = 0;
+    // shmemx_service_fold_loopback's private image of the exchange slots:
+    // the allocation, and its first 4 KiB-aligned byte (host, device)
+    void *loop_raw = nullptr;
+    unsigned char *loop = nullptr, *loop_dev = nullptr;
 } g_svc;
 
 // $SHMEMX_SERVICE: 0 off, 1 on; unset: on unless another PE process of the
@@ -476,6 +480,41 @@ bool serve(void *dst, void *dst2, const void *src, size_t bytes, unsigned long l
     return true;
 }
 
+// One fold request of PE me over the slots at device address `slots` (the
+// job's exchange, or the loopback hook's image of it).
+bool fold_request_of(const void *slots, int me, int type, int op, bool own_order, int start, int logstride,
+                     int size, void *dst, void *dst2, size_t bytes) {
+    const FoldCfg f{type, op, own_order ? 1 : 0, start, logstride, size, me};
+    return serve(dst, dst2, slots, bytes, pack_cfg(f));
+}
+
+constexpr size_t kLoopBytes = node::kMaxPes * node::kXchgSlotBytes;
+constexpr size_t kLoopAlign = 4096;
+
+// The loopback hook's slots: page-locked, device-mapped, 4 KiB-aligned as the
+// job's exchange is; made on first use, freed by service_release.
+bool loop_image() {
+    if (g_svc.loop) return true;
+    void *p = nullptr, *d = nullptr;
+    if (hipHostMalloc(&p, kLoopBytes + kLoopAlign, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipHostFree(p);
+        return false;
+    }
+    const size_t lead = (kLoopAlign - reinterpret_cast<uintptr_t>(d) % kLoopAlign) % kLoopAlign;
+    g_svc.loop_raw = p;
+    g_svc.loop = static_cast<unsigned char *>(p) + lead;
+    g_svc.loop_dev = static_cast<unsigned char *>(d) + lead;
+    return true;
+}
+
+void loop_release() {
+    if (g_svc.loop_raw) (void)hipHostFree(g_svc.loop_raw);
+    g_svc.loop_raw = nullptr;
+    g_svc.loop = g_svc.loop_dev = nullptr;
+}
+
 }  // namespace
 
 bool service_copy(void *dst, void *dst2, const void *src, size_t bytes) {
@@ -487,8 +526,8 @@ bool service_available() { return enabled(); }
 
 void service_fold(int type, int op, bool own_order, int start, int logstride, int size, void *dst, void *dst2,
                   size_t bytes) {
-    const FoldCfg f{type, op, own_order ? 1 : 0, start, logstride, size, g_state.pe};
-    if (!serve(dst, dst2, node::xchg_dev(0), bytes, pack_cfg(f)))
+    if (!fold_request_of(node::xchg_dev(0), g_state.pe, type, op, own_order, start, logstride, size, dst, dst2,
+                         bytes))
         fatal("service workgroup", "a small multi-PE call could not reach the service workgroup");
 }
 
@@ -501,8 +540,9 @@ void service_quiesce() {
 }
 
 void service_release() {
-    if (!g_svc.mb) return;
+    if (!g_svc.mb) return loop_release();
     service_quiesce();
+    loop_release();
     (void)hipStreamDestroy(g_svc.stream);
     (void)hipHostFree(g_svc.mb);
     g_svc.mb = nullptr;
@@ -515,7 +555,45 @@ void device_sync() {
     SHMX_HIP(hipDeviceSynchronize());
 }
 
+// shmemx_service_fold_loopback, after its argument checks: every member's
+// source into its slot of the private image, every other byte of the 64 slots
+// 0xA5, then one fold request of PE me over the image.
+int service_fold_loopback(int type, int op, bool own_order, int start, int logstride, int size, int me, void *dst,
+                          void *dst2, const void *const *srcs, size_t bytes) {
+    if (!g_state.inited || !enabled()) return set_error(SHMEMX_ENOTSUP);
+    bind_device();
+    if (!ensure() || !loop_image()) return set_error(SHMEMX_EDEVICE);
+    std::memset(g_svc.loop, 0xA5, kLoopBytes);
+    for (int i = 0; i < size; ++i)
+        std::memcpy(g_svc.loop + (size_t)(start + (i << logstride)) * node::kXchgSlotBytes, srcs[i], bytes);
+    if (!fold_request_of(g_svc.loop_dev, me, type, op, own_order, start, logstride, size, dst, dst2, bytes))
+        return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}
+
 }  // namespace shmx
+
+// Test hook: one fold request of the small-call exchange in one process.
+extern "C" int shmemx_service_fold_loopback(int type, int op, int own_order, int PE_start, int logPE_stride,
+                                            int PE_size, int me, void *dst, void *dst2, const void *const *srcs,
+                                            size_t nelems) {
+    using namespace shmx;
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!op_valid(type, op) || PE_size < 1 || PE_size > node::kMaxPes || PE_start < 0 || logPE_stride < 0 ||
+        logPE_stride > 7 || PE_start + ((long)(PE_size - 1) << logPE_stride) >= node::kMaxPes ||
+        !is_member(me, PE_start, logPE_stride, PE_size, nullptr) ||
+        nelems > node::kXchgSlotBytes / type_size(type) || !dst)
+        return set_error(SHMEMX_EINVAL);
+    if (nelems > 0) {
+        if (!srcs) return set_error(SHMEMX_EINVAL);
+        for (int i = 0; i < PE_size; ++i)
+            if (!srcs[i]) return set_error(SHMEMX_EINVAL);
+    }
+    if (nelems == 0) return SHMEMX_OK;
+    return service_fold_loopback(type, op, own_order != 0, PE_start, logPE_stride, PE_size, me, dst, dst2, srcs,
+                                 nelems * type_size(type));
+}
 
 extern "C" int shmemx_service_stats(unsigned long long *out, int nout, int reset) {
     std::lock_guard<std::recursive_mutex> lk(shmx::g_mu);

@@ -185,6 +185,8 @@ def lib() -> ctypes.CDLL:
     L.shmemx_direct_stats.restype = i
     L.shmemx_service_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i, i]
     L.shmemx_service_stats.restype = i
+    L.shmemx_service_fold_loopback.argtypes = [i, i, i, i, i, i, i, vp, vp, ctypes.POINTER(vp), sz]
+    L.shmemx_service_fold_loopback.restype = i
     L.shmemx_host_register.argtypes = [vp, sz]
     L.shmemx_host_register.restype = i
     L.shmemx_host_unregister.argtypes = [vp]
@@ -494,6 +496,23 @@ def service_stats(reset: bool = False) -> dict:
     buf = (ctypes.c_ulonglong * len(SERVICE_STATS))()
     k = lib().shmemx_service_stats(buf, len(buf), 1 if reset else 0)
     return {name: buf[i] for i, name in enumerate(SERVICE_STATS[:max(0, k)])}
+
+
+def service_fold_loopback(type_name: str, op: str, dst, srcs, nelems: int, PE_start: int = 0,
+                          logPE_stride: int = 0, me: int | None = None, own_order: bool = False,
+                          dst2=None) -> None:
+    """shmemx_service_fold_loopback: one fold request of the small-call
+    exchange served by the resident workgroup in this process.  srcs: one host
+    array (numpy, or an address) per member of (PE_start, logPE_stride,
+    len(srcs)); me: the member the caller plays (default PE_start); dst, dst2:
+    device-accessible targets.  Blocking."""
+    P = len(srcs)
+    keep = [s for s in srcs]   # the arrays stay alive over the call
+    a = (ctypes.c_void_p * max(P, 1))(*[addr(x) for x in keep])
+    rc = lib().shmemx_service_fold_loopback(TYPES[type_name], OPS[op], 1 if own_order else 0, PE_start,
+                                            logPE_stride, P, PE_start if me is None else me,
+                                            addr(dst), addr(dst2), a, nelems)
+    _check(rc, f"shmemx_service_fold_loopback({type_name},{op},set=({PE_start},{logPE_stride},{P}),me={me})")
 
 
 MIRROR_STATS = ("write_faults", "read_faults", "blocks_flushed", "blocks_fetched",

@@ -353,6 +353,64 @@ def test_fused_loopback_argument_errors_without_a_device(shm):
     assert shm.fused_loopback("double", "sum", 0, [64, 64], [64, 64], 0) == 0
 
 
+def test_service_fold_loopback_argument_errors_without_a_device(shm):
+    """shmemx_service_fold_loopback rejects bad arguments before touching HIP:
+    EINVAL for a pair the reference lacks, PE_size outside 1..64, a negative
+    PE_start, logPE_stride outside 0..7, a last member at 64 or above, a
+    caller outside the set, more elements than one slot holds, a NULL target,
+    and NULL sources or a NULL entry when there are elements; nothing to do
+    for zero elements.  (No call here passes those checks with elements to
+    fold: the fake addresses are never used.)"""
+    import ctypes
+    fn = shm.lib().shmemx_service_fold_loopback
+    D, I = shm.TYPES["double"], shm.TYPES["int"]
+    SUM, XOR, MIN = shm.OPS["sum"], shm.OPS["xor"], shm.OPS["min"]
+    good = (ctypes.c_void_p * 64)(*([64] * 64))
+    hole = (ctypes.c_void_p * 64)(*([64] * 5 + [None] + [64] * 58))
+    EINVAL = 1
+
+    def call(t=D, op=SUM, own=0, start=0, log=0, size=3, me=0, dst=64, dst2=None, srcs=good, n=4):
+        return fn(t, op, own, start, log, size, me, dst, dst2, srcs, n)
+
+    assert call(op=XOR) == EINVAL                                   # not a reference pair
+    assert call(t=shm.TYPES["complexd"], op=MIN) == EINVAL
+    assert call(t=99) == EINVAL
+    for size in (0, -1, 65):
+        assert call(size=size) == EINVAL                            # PE_size outside 1..64
+    assert call(start=-1, me=-1) == EINVAL                          # PE_start < 0
+    assert call(start=-1, me=0) == EINVAL
+    for log in (-1, 8, 31):
+        assert call(log=log, size=1) == EINVAL                      # logPE_stride outside 0..7
+    for start, log, size in ((62, 0, 3), (64, 0, 1), (0, 0, 65), (1, 6, 2), (0, 7, 2), (4, 2, 16), (0, 1, 33)):
+        assert call(start=start, log=log, size=size, me=start) == EINVAL   # a member at 64 or above
+    for start, log, size, me in ((0, 0, 3, 3), (0, 0, 3, -1), (2, 0, 3, 1), (0, 1, 3, 1), (0, 1, 3, 6),
+                                 (4, 2, 3, 6), (0, 0, 64, 64)):
+        assert call(start=start, log=log, size=size, me=me) == EINVAL      # me is no member
+    for name, t in shm.TYPES.items():
+        op = SUM
+        assert call(t=t, op=op, n=4096 // shm.type_size(name) + 1) == EINVAL   # more than a slot
+    assert call(n=2 ** 61) == EINVAL                                # (nelems * size wraps)
+    assert call(dst=None) == EINVAL                                 # NULL target
+    assert call(srcs=None) == EINVAL                                # NULL sources
+    assert call(size=6, srcs=hole) == EINVAL                        # a NULL entry
+    assert call(t=I, op=XOR, size=6, me=5, srcs=hole) == EINVAL
+    assert shm.last_error() == EINVAL
+    # zero elements: nothing to do, whatever the sources
+    assert call(n=0) == 0
+    assert call(n=0, srcs=None) == 0
+    assert call(n=0, size=6, srcs=hole, dst2=64) == 0
+    assert call(n=0, start=63, size=1, me=63, own=1, op=MIN) == 0
+    assert call(n=0, start=1, log=1, size=32, me=63) == 0           # the last member is PE 63
+    assert shm.last_error() == 0
+    # ... but the other checks still hold
+    assert call(n=0, dst=None) == EINVAL
+    assert call(n=0, me=3) == EINVAL
+    with pytest.raises(shm.ShmemError) as e:
+        shm.service_fold_loopback("double", "sum", 64, [64, 64, 0], 4)
+    assert e.value.code == EINVAL
+    shm.service_fold_loopback("double", "sum", 64, [64, 64], 0, PE_start=3, me=4)
+
+
 def test_fused_twoshot_limit_setter(shm):
     """shmemx_set_fused_twoshot_kb returns the previous limit (the 4 MiB
     default unless $SHMEMX_FUSED_TWOSHOT_KB says otherwise) and refuses a

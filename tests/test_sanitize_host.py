@@ -1,7 +1,8 @@
 """The host-compilable parts of the library under AddressSanitizer and
 UndefinedBehaviorSanitizer (gcc, -fno-sanitize-recover: the first report
 fails the run): the symmetric-heap arena (arena.cpp), the intra-node block's
-host barrier and descriptors over forked PEs (node.cpp), the soft x87
+host barrier and descriptors and the small-call exchange's slot protocol over
+forked PEs (node.cpp), the soft x87
 arithmetic the GPU runs for long double (ld80.h), and the copy threads'
 placement over a fake sysfs tree (topology.cpp), the staging chunk
 schedule (stage_plan.h), the active-set geometry (set_geom.h) and the staging
@@ -25,6 +26,9 @@ CASES = {
     "arena": ([os.path.join(NATIVE, "test_heap.cpp"), os.path.join(CSRC, "arena.cpp")], [], ["50000"], "ok 50000"),
     "node": ([os.path.join(NATIVE, "test_node_barrier.cpp"), os.path.join(CSRC, "node.cpp")], HIP_LINK,
              ["4", "1000"], "ok 4"),
+    # the small-call exchange's slot protocol over forked PEs (node.cpp xchg_claim / xchg_finish)
+    "xchg": ([os.path.join(NATIVE, "test_xchg.cpp"), os.path.join(CSRC, "node.cpp")], HIP_LINK,
+             ["4", "1000"], "ok 1000 calls"),
     "ld80": ([os.path.join(NATIVE, "test_ld80.cpp")], [], ["300000"], "ok 300000"),
     # the host staging pipeline's chunk schedule (stage_plan.h)
     "stage_plan": ([os.path.join(NATIVE, "test_stage_plan.cpp")], [], [], "ok "),
