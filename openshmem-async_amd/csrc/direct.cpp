@@ -414,18 +414,16 @@ int direct_fused(int type, int op, char *tgt, size_t n, const ActiveSet &set, in
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer region (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
-    SignalFoldArgs fa{};
-    if (!signal_args(set, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
-    fa.gsync = fence_records().gsync;
+    SignalArgs sa;
+    if (!signal_args(set, &sa)) fatal("DIRECT", "a mapped peer heap went missing");
     const size_t sz = type_size(type);
     char *const scratch_tgt = g_scratch.base + g_scratch.bytes / 2;
-    fa.out = stage_tgt ? scratch_tgt : tgt;
     // set order, or mine (src_me first, then the others ascending)
-    fold_inputs(fa.ins, P, m, own_order, [&](int i) {
+    const void *ins[kMaxFoldInputs];
+    fold_inputs(ins, P, m, own_order, [&](int i) {
         return node::peer_base(static_cast<node::Region>(desc[i].src.region), set.pe_of(i)) + desc[i].src.off;
     });
-    fa.nins = P;
-    fa.n = n;
+    SignalFoldArgs fa = fused_args(sa, stage_tgt ? scratch_tgt : tgt, ins, P, n);
     // The host spins on a page-locked word instead of waiting for the
     // stream: the kernel stores it itself when one workgroup did all the
     // work (an array of at most 4 elements per lane of one block: the ISx
@@ -460,19 +458,14 @@ int direct_fused2(int type, int op, char *tgt, size_t n, const ActiveSet &set, i
         trace(LOG_REDUCTION, "DIRECT: a member could not map a peer heap (%s)", node::last_ipc_error());
         return set_error(SHMEMX_ENOTSUP);
     }
-    SignalFoldArgs fa{};
-    if (!signal_args(set, &fa.sig)) fatal("DIRECT", "a mapped peer heap went missing");
-    fa.gsync = fence_records().gsync;
+    SignalArgs sa;
+    if (!signal_args(set, &sa)) fatal("DIRECT", "a mapped peer heap went missing");
+    const void *ins[kMaxFoldInputs];
+    for (int i = 0; i < P; ++i) ins[i] = node::peer_base(node::kHeap, set.pe_of(i)) + desc[i].src.off;
+    SignalFoldArgs fa = fused_args(sa, tgt, ins, P, n);
     const Slices sl(n, P, type_size(type));
-    fa.out = tgt;
-    for (int i = 0; i < P; ++i) fa.ins[i] = node::peer_base(node::kHeap, set.pe_of(i)) + desc[i].src.off;
-    fa.nins = P;
-    fa.n = n;
-    fa.two_shot = 1;
-    fa.lo = sl.lo(m);
-    fa.hi = sl.hi(m);
     auto tgt_of = [&](int i) { return node::peer_base(node::kHeap, set.pe_of(i)) + desc[i].tgt.off; };
-    fa.nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa.gsrc, fa.gdst, fa.glen);
+    two_shot_args(&fa, sl, m, tgt_of, tgt);
     const double t0 = now_us();
     SHMX_HIP(launch_signal_fold(type, op, fa, s));   // reduce-op.c:217-250
     const HostSignal sig = next_host_signal();       // a marker: the host spins, no stream wait

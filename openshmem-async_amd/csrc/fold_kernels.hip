@@ -162,32 +162,31 @@ __device__ __forceinline__ void signal_host_done(const FoldArgs &args) {
         __hip_atomic_store(args.sig_word, args.sig_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// f(i) for every element i of the scalar head and tail, grid-stride: the
+// whole array when the operands do not share one alignment.
+template <typename T, typename F>
+__device__ __forceinline__ void for_scalar_edges(const FoldArgs &args, size_t tid, size_t nthr, F f) {
+    constexpr int E = 16 / sizeof(T);
+    const size_t body_end = args.head + args.nvec * E;
+    const size_t nscalar = args.head + args.tail;
+    for (size_t s = tid; s < nscalar; s += nthr) f(s < args.head ? s : body_end + (s - args.head));
+}
 
 // NIN > 0: number of inputs fixed at compile time (all loads hoisted);
 // NIN == 0: runtime args.nins.
 template <typename T, int OP, int NIN, int UNROLL, int NT>
 __device__ __forceinline__ void fold_body(const FoldArgs &args) {
-    constexpr int E = 16 / sizeof(T);
     const int nins = NIN > 0 ? NIN : args.nins;
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const size_t nthr = (size_t)gridDim.x * kBlock;
 
-    // Scalar head and tail (grid-stride: the whole array when the inputs
-    // do not share one alignment).
-    {
-        T *out = static_cast<T *>(args.out);
-        const size_t body_end = args.head + args.nvec * E;
-        const size_t nscalar = args.head + args.tail;
-        for (size_t s = tid; s < nscalar; s += nthr) {
-            const size_t i = s < args.head ? s : body_end + (s - args.head);
-            T acc = static_cast<const T *>(args.ins[0])[i];
-            for (int k = 1; k < nins; ++k)
-                acc = Op<T, OP>::ap(acc, static_cast<const T *>(args.ins[k])[i]);
-            out[i] = acc;
-            if constexpr (NIN == 1)
-                if (args.out2) static_cast<T *>(args.out2)[i] = acc;
-        }
-    }
+    for_scalar_edges<T>(args, tid, nthr, [&](size_t i) {
+        T acc = static_cast<const T *>(args.ins[0])[i];
+        for (int k = 1; k < nins; ++k) acc = Op<T, OP>::ap(acc, static_cast<const T *>(args.ins[k])[i]);
+        static_cast<T *>(args.out)[i] = acc;
+        if constexpr (NIN == 1)
+            if (args.out2) static_cast<T *>(args.out2)[i] = acc;
+    });
     if (args.nvec == 0) return;
 
     u32x4 *out = reinterpret_cast<u32x4 *>(static_cast<T *>(args.out) + args.head);
@@ -306,22 +305,15 @@ constexpr int peers_unroll(int maxin) { return maxin <= 8 ? 4 : 2; }
 
 template <typename T, int OP, int MAXIN, int NT>
 __global__ __launch_bounds__(kBlock) void fold_peers_kernel(FoldArgs args) {
-    constexpr int E = 16 / sizeof(T);
     constexpr int U = peers_unroll(MAXIN);
     const int nins = args.nins;
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const size_t nthr = (size_t)gridDim.x * kBlock;
-    {
-        T *out = static_cast<T *>(args.out);
-        const size_t body_end = args.head + args.nvec * E;
-        const size_t nscalar = args.head + args.tail;
-        for (size_t s = tid; s < nscalar; s += nthr) {
-            const size_t i = s < args.head ? s : body_end + (s - args.head);
-            T acc = static_cast<const T *>(args.ins[0])[i];
-            for (int k = 1; k < nins; ++k) acc = Op<T, OP>::ap(acc, static_cast<const T *>(args.ins[k])[i]);
-            out[i] = acc;
-        }
-    }
+    for_scalar_edges<T>(args, tid, nthr, [&](size_t i) {
+        T acc = static_cast<const T *>(args.ins[0])[i];
+        for (int k = 1; k < nins; ++k) acc = Op<T, OP>::ap(acc, static_cast<const T *>(args.ins[k])[i]);
+        static_cast<T *>(args.out)[i] = acc;
+    });
     if (args.nvec == 0) return;
     auto in = [&](int k) {
         return reinterpret_cast<const u32x4 *>(static_cast<const T *>(args.ins[k]) + args.head);
@@ -438,6 +430,8 @@ __global__ __launch_bounds__(kBlock) void fold_orders_kernel(OrdersArgs args) {
     const int nins = args.nins;
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const size_t nthr = (size_t)gridDim.x * kBlock;
+    // for_scalar_edges' loop, written out: through the helper the double
+    // MAXIN 16 instances allocate registers differently (141 -> 140 VGPRs)
     {
         const size_t body_end = args.head + args.nvec * E;
         const size_t nscalar = args.head + args.tail;
@@ -469,20 +463,10 @@ __global__ __launch_bounds__(kBlock) void fold_orders_kernel(OrdersArgs args) {
 }
 
 
-// One chunk of kBlock x unroll vectors per block (persistent grids, caps and
-// XCD remaps measured no faster: DESIGN_history.md §4.2); the scalar-only
-// case (inputs of different alignment) grid-strides over at most 2048 blocks.
-static size_t grid_for(const FoldArgs &a, int unroll) {
-    size_t work_blocks;
-    if (a.nvec > 0)
-        work_blocks = (a.nvec + (size_t)kBlock * unroll - 1) / ((size_t)kBlock * unroll);
-    else
-        work_blocks = (a.head + a.tail + kBlock - 1) / kBlock;
-    const size_t cap = a.nvec == 0 ? 2048 : (size_t)1 << 30;
-    size_t blocks = work_blocks < cap ? work_blocks : cap;
-    if (blocks < 1) blocks = 1;
-    if (blocks > (size_t)INT_MAX) blocks = INT_MAX;
-    return blocks;
+// The grid of a launch over args (FoldArgs or OrdersArgs): span16.h's rule.
+template <typename Args>
+size_t grid_for(const Args &a, int unroll) {
+    return span_blocks(Span16{a.head, a.nvec, a.tail}, unroll);
 }
 
 // The marker after the work: the stream's own value write (the command
@@ -580,14 +564,14 @@ hipError_t launch_nt(const FoldArgs &a, hipStream_t stream) {
 // 83.7 us at 256 MiB, 166.6 us at 512 MiB (6.41-6.44 TB/s).
 // Default-policy stores look faster by kernel time alone (6.9-7.1) but leave
 // up to 256 MiB dirty in the Infinity Cache for the next kernel to write back
-// (4.9-5.2 TB/s charged), so the stores stay non-temporal.
-constexpr int kUnrollCopy = 8;       // small copies: one workgroup up to 32 KiB
-constexpr int kUnrollCopyLarge = 1;  // large copies: 4 KiB per workgroup
-
+// (4.9-5.2 TB/s charged), so the stores stay non-temporal.  kUnrollCopy,
+// kUnrollCopyLarge and the choice between them are span16.h's (copy_small,
+// copy_blocks), which copy_one_workgroup evaluates too.
 template <typename T, int NT>
 hipError_t launch_copy_nt(const FoldArgs &a0, hipStream_t stream) {
-    const bool small = a0.nvec <= (size_t)kBlock * kUnrollCopy;
-    const size_t blocks = grid_for(a0, small ? kUnrollCopy : kUnrollCopyLarge);
+    const Span16 span{a0.head, a0.nvec, a0.tail};
+    const bool small = copy_small(span);
+    const size_t blocks = copy_blocks(span);
     // a one-workgroup copy stores the host signal itself (launch_fold_signal);
     // a larger grid is followed by the marker kernel
     const bool self_signal = a0.sig_word && blocks == 1;
@@ -611,38 +595,6 @@ hipError_t launch_copy(const FoldArgs &a, hipStream_t stream) {
                                                   : launch_copy_nt<T, 0>(a, stream);
 }
 
-template <typename T>
-hipError_t launch_int_ops(int op, const FoldArgs &a, hipStream_t s) {
-    switch (op) {
-    case SHMEMX_OP_SUM: return launch_nt<T, SHMEMX_OP_SUM>(a, s);
-    case SHMEMX_OP_PROD: return launch_nt<T, SHMEMX_OP_PROD>(a, s);
-    case SHMEMX_OP_AND: return launch_nt<T, SHMEMX_OP_AND>(a, s);
-    case SHMEMX_OP_OR: return launch_nt<T, SHMEMX_OP_OR>(a, s);
-    case SHMEMX_OP_XOR: return launch_nt<T, SHMEMX_OP_XOR>(a, s);
-    case SHMEMX_OP_MIN: return launch_nt<T, SHMEMX_OP_MIN>(a, s);
-    case SHMEMX_OP_MAX: return launch_nt<T, SHMEMX_OP_MAX>(a, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-template <typename T>
-hipError_t launch_fp_ops(int op, const FoldArgs &a, hipStream_t s) {
-    switch (op) {
-    case SHMEMX_OP_SUM: return launch_nt<T, SHMEMX_OP_SUM>(a, s);
-    case SHMEMX_OP_PROD: return launch_nt<T, SHMEMX_OP_PROD>(a, s);
-    case SHMEMX_OP_MIN: return launch_nt<T, SHMEMX_OP_MIN>(a, s);
-    case SHMEMX_OP_MAX: return launch_nt<T, SHMEMX_OP_MAX>(a, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-template <typename T>
-hipError_t launch_cplx_ops(int op, const FoldArgs &a, hipStream_t s) {
-    switch (op) {
-    case SHMEMX_OP_SUM: return launch_nt<T, SHMEMX_OP_SUM>(a, s);
-    case SHMEMX_OP_PROD: return launch_nt<T, SHMEMX_OP_PROD>(a, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 size_t type_size(int type) {
@@ -662,42 +614,27 @@ size_t type_size(int type) {
 
 bool op_valid(int type, int op) {
     if (type < 0 || type >= SHMEMX_NTYPES || op < 0 || op >= SHMEMX_NOPS) return false;
-    switch (op) {
-    case SHMEMX_OP_SUM:
-    case SHMEMX_OP_PROD: return true;
-    case SHMEMX_OP_AND:
-    case SHMEMX_OP_OR:
-    case SHMEMX_OP_XOR: return type <= SHMEMX_TYPE_LONGLONG;
-    default: return type != SHMEMX_TYPE_COMPLEXD && type != SHMEMX_TYPE_COMPLEXF;
-    }
+    return with_type_op(type, op, [](auto, auto) {});
 }
 
 bool op_on_device(int type, int op) { return op_valid(type, op); }
 
 namespace {
 
-// Split n elements into scalar head, 16-B vector body and scalar tail, given
-// every array's address (the body only if all share one offset mod 16 that is
-// a whole number of elements), then dispatch on type.
-hipError_t dispatch(int type, int op, FoldArgs &a, const void *const *ptrs, int nptrs, size_t n,
-                    hipStream_t stream) {
+// Split a's n elements into scalar head, 16-B vector body and scalar tail
+// over every array of the call (split16; a copy's second destination too:
+// the vector body needs all of them on one alignment), then dispatch on type.
+hipError_t dispatch(int type, int op, FoldArgs &a, size_t n, hipStream_t stream) {
     const size_t sz = type_size(type);
-    const uintptr_t off = reinterpret_cast<uintptr_t>(ptrs[0]) & 15u;
-    bool same = (off % sz) == 0;
-    for (int k = 1; k < nptrs && same; ++k)
-        same = (reinterpret_cast<uintptr_t>(ptrs[k]) & 15u) == off;
-    if (same) {
-        size_t head = ((16 - off) & 15u) / sz;
-        if (head > n) head = n;
-        const size_t E = 16 / sz;
-        a.head = head;
-        a.nvec = (n - head) / E;
-        a.tail = n - head - a.nvec * E;
-    } else {
-        a.head = n;
-        a.nvec = 0;
-        a.tail = 0;
-    }
+    const void *ptrs[kMaxFoldInputs + 2];
+    int nptrs = 0;
+    ptrs[nptrs++] = a.out;
+    if (a.out2) ptrs[nptrs++] = a.out2;
+    for (int k = 0; k < a.nins; ++k) ptrs[nptrs++] = a.ins[k];
+    const Span16 span = split16(ptrs, nptrs, sz, n);
+    a.head = span.head;
+    a.nvec = span.nvec;
+    a.tail = span.tail;
     if (a.nins == 1) {   // a copy: bits only, one kernel per element size
         switch (sz) {
         case 2: return launch_copy<short>(a, stream);
@@ -707,71 +644,50 @@ hipError_t dispatch(int type, int op, FoldArgs &a, const void *const *ptrs, int 
         default: return hipErrorInvalidValue;
         }
     }
-    switch (type) {
-    case SHMEMX_TYPE_SHORT: return launch_int_ops<short>(op, a, stream);
-    case SHMEMX_TYPE_INT: return launch_int_ops<int>(op, a, stream);
-    case SHMEMX_TYPE_LONG:
-    case SHMEMX_TYPE_LONGLONG: return launch_int_ops<long>(op, a, stream);
-    case SHMEMX_TYPE_FLOAT: return launch_fp_ops<float>(op, a, stream);
-    case SHMEMX_TYPE_DOUBLE: return launch_fp_ops<double>(op, a, stream);
-    case SHMEMX_TYPE_LONGDOUBLE: return launch_fp_ops<ld80>(op, a, stream);
-    case SHMEMX_TYPE_COMPLEXD: return launch_cplx_ops<cplxd>(op, a, stream);
-    case SHMEMX_TYPE_COMPLEXF: return launch_cplx_ops<cplxf>(op, a, stream);
-    default: return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    with_type_op(type, op, [&](auto t, auto o) {
+        e = launch_nt<typename decltype(t)::type, decltype(o)::value>(a, stream);
+    });
+    return e;
+}
+
+// launch_fold, launch_fold_signal (sig.word set) and launch_fold_peers: the
+// call checked, its FoldArgs filled in, dispatched.
+hipError_t launch_fold_args(int type, int op, void *out, const void *const *ins, int nins, size_t n, int peers,
+                            const HostSignal &sig, hipStream_t stream) {
+    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out) return hipErrorInvalidValue;
+    if (n == 0) return sig.word ? launch_host_signal(sig, stream) : hipSuccess;
+    FoldArgs a{};
+    a.out = out;
+    a.nins = nins;
+    a.peers = peers;
+    a.sig_word = sig.word;
+    a.sig_value = sig.value;
+    for (int k = 0; k < nins; ++k) {
+        if (!ins[k]) return hipErrorInvalidValue;
+        a.ins[k] = ins[k];
     }
+    return dispatch(type, op, a, n, stream);
 }
 
 }  // namespace
 
 hipError_t launch_fold(int type, int op, void *out, const void *const *ins,
                        int nins, size_t n, hipStream_t stream) {
-    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out)
-        return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
-    FoldArgs a{};
-    a.out = out;
-    a.nins = nins;
-    const void *ptrs[kMaxFoldInputs + 1];
-    ptrs[0] = out;
-    for (int k = 0; k < nins; ++k) {
-        if (!ins[k]) return hipErrorInvalidValue;
-        a.ins[k] = ins[k];
-        ptrs[k + 1] = ins[k];
-    }
-    return dispatch(type, op, a, ptrs, nins + 1, n, stream);
+    return launch_fold_args(type, op, out, ins, nins, n, 0, HostSignal{nullptr, 0}, stream);
 }
 
 bool copy_one_workgroup(int type, const void *dst, const void *src, size_t n) {
     const size_t sz = type_size(type);
     if (!sz || !n) return false;
-    const uintptr_t off = reinterpret_cast<uintptr_t>(dst) & 15u;
-    if (off % sz != 0 || (reinterpret_cast<uintptr_t>(src) & 15u) != off)
-        return n <= (size_t)kBlock;                    // all scalar: ceil(n / kBlock) blocks
-    size_t head = ((16 - off) & 15u) / sz;
-    if (head > n) head = n;
-    const size_t E = 16 / sz, nvec = (n - head) / E, tail = n - head - nvec * E;
-    if (nvec == 0) return head + tail <= (size_t)kBlock;
-    return nvec <= (size_t)kBlock * kUnrollCopy;       // grid_for: one chunk per block
+    const void *ptrs[2] = {dst, src};
+    return copy_blocks(split16(ptrs, 2, sz, n)) == 1;   // launch_copy_nt's grid
 }
 
 hipError_t launch_fold_signal(int type, int op, void *out, const void *const *ins, int nins, size_t n,
                               hipStream_t stream, const HostSignal &sig) {
-    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out || !sig.word)
-        return hipErrorInvalidValue;
-    if (n == 0) return launch_host_signal(sig, stream);
-    FoldArgs a{};
-    a.out = out;
-    a.nins = nins;
-    a.sig_word = sig.word;
-    a.sig_value = sig.value;
-    const void *ptrs[kMaxFoldInputs + 1];
-    ptrs[0] = out;
-    for (int k = 0; k < nins; ++k) {
-        if (!ins[k]) return hipErrorInvalidValue;
-        a.ins[k] = ins[k];
-        ptrs[k + 1] = ins[k];
-    }
-    return dispatch(type, op, a, ptrs, nins + 1, n, stream);
+    if (!sig.word) return hipErrorInvalidValue;
+    return launch_fold_args(type, op, out, ins, nins, n, 0, sig, stream);
 }
 
 hipError_t launch_copy2_signal(int type, void *out, void *out2, const void *in, size_t n, hipStream_t stream,
@@ -785,8 +701,7 @@ hipError_t launch_copy2_signal(int type, void *out, void *out2, const void *in, 
     a.ins[0] = in;
     a.sig_word = sig.word;
     a.sig_value = sig.value;
-    const void *ptrs[3] = {out, out2, in};   // the vector body needs all three on one alignment
-    return dispatch(type, SHMEMX_OP_SUM, a, ptrs, 3, n, stream);
+    return dispatch(type, SHMEMX_OP_SUM, a, n, stream);
 }
 
 hipError_t launch_host_signal(const HostSignal &sig, hipStream_t stream) {
@@ -796,21 +711,7 @@ hipError_t launch_host_signal(const HostSignal &sig, hipStream_t stream) {
 
 hipError_t launch_fold_peers(int type, int op, void *out, const void *const *ins, int nins, size_t n,
                              hipStream_t stream) {
-    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out)
-        return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
-    FoldArgs a{};
-    a.out = out;
-    a.nins = nins;
-    a.peers = 1;
-    const void *ptrs[kMaxFoldInputs + 1];
-    ptrs[0] = out;
-    for (int k = 0; k < nins; ++k) {
-        if (!ins[k]) return hipErrorInvalidValue;
-        a.ins[k] = ins[k];
-        ptrs[k + 1] = ins[k];
-    }
-    return dispatch(type, op, a, ptrs, nins + 1, n, stream);
+    return launch_fold_args(type, op, out, ins, nins, n, 1, HostSignal{nullptr, 0}, stream);
 }
 
 // ------------------------------------------------------- the P-order fold
@@ -818,12 +719,8 @@ namespace {
 
 template <typename T, int OP, int MAXIN, int NT>
 void launch_orders_grid(const OrdersArgs &a, hipStream_t stream) {
-    FoldArgs g{};
-    g.head = a.head;
-    g.nvec = a.nvec;
-    g.tail = a.tail;
     launch_k(kKindOrders, fold_orders_kernel<T, OP, MAXIN, NT>,
-             dim3((unsigned)grid_for(g, kUnrollOrders)), dim3(kBlock), stream, a);
+             dim3((unsigned)grid_for(a, kUnrollOrders)), dim3(kBlock), stream, a);
 }
 
 // P reads and P writes of n elements: non-temporal from 32 MiB moved, as the
@@ -841,12 +738,6 @@ hipError_t launch_orders_typed(const OrdersArgs &a, size_t n, hipStream_t stream
     return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_orders_ops(int op, const OrdersArgs &a, size_t n, hipStream_t stream) {
-    return op == SHMEMX_OP_MIN ? launch_orders_typed<T, SHMEMX_OP_MIN>(a, n, stream)
-                               : launch_orders_typed<T, SHMEMX_OP_MAX>(a, n, stream);
-}
-
 }  // namespace
 
 hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
@@ -854,34 +745,30 @@ hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *c
     if ((op != SHMEMX_OP_MIN && op != SHMEMX_OP_MAX) || nins < 1 || nins > kMaxFoldInputs || !outs || !ins)
         return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    const size_t sz = type_size(type);
     OrdersArgs a{};
     a.nins = nins;
-    // the vector body only if all 2 P arrays share one offset mod 16 that is
-    // a whole number of elements (dispatch's rule)
-    const uintptr_t off = reinterpret_cast<uintptr_t>(ins[0]) & 15u;
-    bool same = sz && (off % sz) == 0;
+    const void *ptrs[2 * kMaxFoldInputs];
     for (int k = 0; k < nins; ++k) {
         if (!ins[k] || !outs[k]) return hipErrorInvalidValue;
-        a.ins[k] = ins[k];
-        a.outs[k] = outs[k];
-        same = same && (reinterpret_cast<uintptr_t>(ins[k]) & 15u) == off &&
-               (reinterpret_cast<uintptr_t>(outs[k]) & 15u) == off;
+        ptrs[2 * k] = a.ins[k] = ins[k];
+        ptrs[2 * k + 1] = a.outs[k] = outs[k];
     }
-    if (same) {
-        const size_t E = 16 / sz;
-        a.head = std::min(n, ((16 - off) & 15u) / sz);
-        a.nvec = (n - a.head) / E;
-        a.tail = n - a.head - a.nvec * E;
-    } else {
-        a.head = n;
-    }
-    switch (type) {
-    case SHMEMX_TYPE_FLOAT: return launch_orders_ops<float>(op, a, n, stream);
-    case SHMEMX_TYPE_DOUBLE: return launch_orders_ops<double>(op, a, n, stream);
-    case SHMEMX_TYPE_LONGDOUBLE: return launch_orders_ops<ld80>(op, a, n, stream);
-    default: return hipErrorInvalidValue;
-    }
+    // the vector body only if all 2 P arrays share one alignment
+    const Span16 span = split16(ptrs, 2 * nins, type_size(type), n);
+    a.head = span.head;
+    a.nvec = span.nvec;
+    a.tail = span.tail;
+    hipError_t e = hipErrorInvalidValue;
+    with_type_op(type, op, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        constexpr int OP = decltype(o)::value;
+        // the pairs whose answer depends on the order (own_order_pair)
+        if constexpr ((std::is_same<T, float>::value || std::is_same<T, double>::value ||
+                       std::is_same<T, ld80>::value) &&
+                      (OP == SHMEMX_OP_MIN || OP == SHMEMX_OP_MAX))
+            e = launch_orders_typed<T, OP>(a, n, stream);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------ gather copy

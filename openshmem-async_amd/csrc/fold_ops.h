@@ -15,6 +15,7 @@
 #include "internal.h"
 #include "ld80.h"
 #include "shmem_reduce_mi355x.h"
+#include "span16.h"   // kBlock
 
 namespace shmx {
 
@@ -165,7 +166,62 @@ __device__ __forceinline__ u32x4 apply16(u32x4 a, u32x4 b) {
     return x.v;
 }
 
-constexpr int kBlock = 256;  // 4 waves of 64
+// ------------------------------------------------- the (type, op) table
+// Which pairs the reference defines, and the C++ type that runs each: the
+// one place a new type or op is added.  with_type_op calls
+// f(TypeTag<T>{}, OpTag<OP>{}) for a defined pair and returns false for any
+// other; long and long long are both 8 bytes on LP64 and run as long.
+template <typename T> struct TypeTag { using type = T; };
+template <int OP> struct OpTag { static constexpr int value = OP; };
+
+template <typename F>
+__host__ __device__ __forceinline__ bool with_type(int type, F &&f) {
+    switch (type) {
+    case SHMEMX_TYPE_SHORT: return f(TypeTag<short>{});
+    case SHMEMX_TYPE_INT: return f(TypeTag<int>{});
+    case SHMEMX_TYPE_LONG:
+    case SHMEMX_TYPE_LONGLONG: return f(TypeTag<long>{});
+    case SHMEMX_TYPE_FLOAT: return f(TypeTag<float>{});
+    case SHMEMX_TYPE_DOUBLE: return f(TypeTag<double>{});
+    case SHMEMX_TYPE_LONGDOUBLE: return f(TypeTag<ld80>{});
+    case SHMEMX_TYPE_COMPLEXD: return f(TypeTag<cplxd>{});
+    case SHMEMX_TYPE_COMPLEXF: return f(TypeTag<cplxf>{});
+    default: return false;
+    }
+}
+
+// integers: all seven ops; real floating types: no bitwise ops; complex: sum
+// and prod only (the Op<T, OP> specialisations above)
+template <typename T, typename F>
+__host__ __device__ __forceinline__ bool with_op(int op, F &&f) {
+    constexpr bool bitwise = std::is_integral<T>::value;
+    constexpr bool ordered = !std::is_same<T, cplxd>::value && !std::is_same<T, cplxf>::value;
+#define SHMX_OP_CASE(OP, defined)          \
+    case OP:                               \
+        if constexpr (defined) {           \
+            f(OpTag<OP>{});                \
+            return true;                   \
+        }                                  \
+        return false;
+    switch (op) {
+        SHMX_OP_CASE(SHMEMX_OP_SUM, true)
+        SHMX_OP_CASE(SHMEMX_OP_PROD, true)
+        SHMX_OP_CASE(SHMEMX_OP_AND, bitwise)
+        SHMX_OP_CASE(SHMEMX_OP_OR, bitwise)
+        SHMX_OP_CASE(SHMEMX_OP_XOR, bitwise)
+        SHMX_OP_CASE(SHMEMX_OP_MIN, ordered)
+        SHMX_OP_CASE(SHMEMX_OP_MAX, ordered)
+    default: return false;
+    }
+#undef SHMX_OP_CASE
+}
+
+template <typename F>
+__host__ __device__ __forceinline__ bool with_type_op(int type, int op, F &&f) {
+    return with_type(type, [&](auto t) {
+        return with_op<typename decltype(t)::type>(op, [&](auto o) { f(t, o); });
+    });
+}
 
 // long double and the complex products: soft-float / Annex G code unrolled
 // 16 vectors deep would spill; they keep the runtime-nins kernel.

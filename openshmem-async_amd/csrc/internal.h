@@ -176,8 +176,8 @@ hipError_t launch_checksum(int type, const void *ptr, size_t n, unsigned long lo
 // shmemx_kernel_times): while on, every fold-family launch carries a
 // start / stop event pair of its own dispatch (hipExtLaunchKernelGGL), up to
 // 4096 launches between reads.  kernel_times waits for them and returns
-// their durations (us) and kinds (0 fold, 1 copy, 2 peers fold, 3 gather)
-// in launch order, then starts over.
+// their durations (us) and kinds (0 fold, 1 copy, 2 peers fold, 3 gather,
+// 4 P-order fold) in launch order, then starts over.
 int kernel_timing(int on);
 int kernel_times(double *us, int *kind, int max, unsigned long long *dropped);
 

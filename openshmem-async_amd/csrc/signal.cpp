@@ -90,10 +90,6 @@ void check_signal_error(const char *what) {
     }
 }
 
-namespace {
-
-// A fused launch (launch_signal_fold) of the P sources ins into out: the one
-// shot as it stands, the two shot after two_shot_args.
 SignalFoldArgs fused_args(const SignalArgs &sa, void *out, const void *const *ins, int P, size_t n) {
     SignalFoldArgs fa{};
     fa.sig = sa;
@@ -104,19 +100,6 @@ SignalFoldArgs fused_args(const SignalArgs &sa, void *out, const void *const *in
     fa.n = n;
     return fa;
 }
-
-// The fused two shot of member m: fold slice m (set order: fa->ins holds
-// every source in it), then gather the other non-empty slices, ascending,
-// from the members' targets tgt_of(i) into tgt.
-template <class TgtOf>
-void two_shot_args(SignalFoldArgs *fa, const Slices &sl, int m, TgtOf tgt_of, char *tgt) {
-    fa->two_shot = 1;
-    fa->lo = sl.lo(m);
-    fa->hi = sl.hi(m);
-    fa->nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa->gsrc, fa->gdst, fa->glen);
-}
-
-}  // namespace
 
 int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s) {

@@ -28,6 +28,21 @@ __global__ __launch_bounds__(64) void sys_fence_kernel(unsigned int *seen) {
     }
 }
 
+// One whole wave, lane b holding block b's record (0: none): the XCDs that
+// reported, counted; fewer than the device has is error word 2.
+__device__ __forceinline__ void count_coverage(const SignalArgs &a, unsigned int rec) {
+    int covered = 0;
+#pragma unroll
+    for (unsigned int x = 0; x < 16; ++x) covered += __ballot(rec == (kFenceSeen | x)) != 0 ? 1 : 0;
+    if (threadIdx.x == 0) {
+        atomicAdd(a.fence_stats, 1ull);
+        if (covered < a.nxcc) {
+            atomicAdd(a.fence_stats + 1, 1ull);
+            __hip_atomic_store(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
 __device__ __forceinline__ void check_fence(const SignalArgs &a) {
     // lane b reads block b's record of the fence just before this kernel
     const int lane = threadIdx.x;
@@ -37,17 +52,7 @@ __device__ __forceinline__ void check_fence(const SignalArgs &a) {
         __hip_atomic_store(a.seen + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (!a.seen) return;
-    int covered = 0;
-#pragma unroll
-    for (unsigned int x = 0; x < 16; ++x)
-        covered += __ballot(rec == (kFenceSeen | x)) != 0 ? 1 : 0;
-    if (lane == 0) {
-        atomicAdd(a.fence_stats, 1ull);
-        if (covered < a.nxcc) {
-            atomicAdd(a.fence_stats + 1, 1ull);
-            __hip_atomic_store(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    count_coverage(a, rec);
 }
 
 __global__ __launch_bounds__(64) void signal_kernel(SignalArgs a) {
@@ -118,18 +123,21 @@ __device__ __forceinline__ T fold_elem(const SignalFoldArgs &a, size_t i) {
     }
 }
 
-template <typename T, int OP>
-__global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
+// The entry of a fused launch, one shot and two shot: every block records
+// its XCD, fences and arrives at the self-resetting grid barrier (gsync: an
+// arrival counter and a generation); the last block to arrive checks the XCD
+// coverage, does the entry handshake with the peers (reduce-op.c:217: every
+// source is final) and releases the generation.  wait: a block that is not
+// the last waits for that release; without it such a block returns at once
+// (false), having fenced and arrived, and must leave.  Returns whether this
+// block was the last to arrive; *gen0 is the generation the launch found.
+__device__ __forceinline__ bool fused_entry(const SignalFoldArgs &a, bool wait, unsigned int *gen0_out) {
     unsigned int *const count = a.gsync, *const gen = a.gsync + 1;
-    // up to 4 elements per lane of one block: the last block to arrive folds
-    // alone, and no block waits for a release or arrives at the exit
-    const bool tiny = a.n <= kFusedTinyElems;
-    static_assert(kFusedTinyElems == (size_t)4 * kBlock, "the tiny case is 4 elements per lane of one block");
     __shared__ int s_last;
     __shared__ unsigned int s_gen0;
     if (threadIdx.x == 0) {
-        // entry: record this block's XCD, then write back the XCD's L2 and
-        // drop stale peer lines (the fence also orders the record), arrive
+        // record this block's XCD, then write back the XCD's L2 and drop
+        // stale peer lines (the fence also orders the record), arrive
         const unsigned int xcc = (unsigned int)__builtin_amdgcn_s_getreg(kXccIdReg) & 15u;
         __hip_atomic_store(a.sig.seen + blockIdx.x, kFenceSeen | xcc, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
@@ -137,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
         const unsigned int gen0 = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned int old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = old == gridDim.x - 1;
-        if (!s_last && !tiny) {
+        if (!s_last && wait) {
             // relaxed polls (an acquire load would invalidate the L2 on every
             // poll), one acquire once the generation moved
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -149,17 +157,15 @@ __global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
                 }
                 __builtin_amdgcn_s_sleep(2);
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        } else if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
+        if (s_last || wait) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         s_gen0 = gen0;   // for the checking wave
     }
     __syncthreads();
-    // a tiny array is folded by the last block alone: the others have fenced
-    // and arrived, and leave
-    if (tiny && !s_last) return;
-    if (s_last && threadIdx.x < 64) {
+    const bool last = s_last;
+    *gen0_out = s_gen0;
+    if (!last && !wait) return false;
+    if (last && threadIdx.x < 64) {
         // the last block's first wave: every block's XCD record at once (lane
         // b reads block b's), then lane 0 does the entry handshake
         const int lane = threadIdx.x;
@@ -168,21 +174,39 @@ __global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
             rec = __hip_atomic_load(a.sig.seen + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(a.sig.seen + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        int covered = 0;
-#pragma unroll
-        for (unsigned int x = 0; x < 16; ++x) covered += __ballot(rec == (kFenceSeen | x)) != 0 ? 1 : 0;
+        count_coverage(a.sig, rec);
         if (lane == 0) {
-            atomicAdd(a.sig.fence_stats, 1ull);
-            if (covered < a.sig.nxcc) {
-                atomicAdd(a.sig.fence_stats + 1, 1ull);
-                __hip_atomic_store(a.sig.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            peer_handshake(a.sig);   // reduce-op.c:217
+            peer_handshake(a.sig);
             __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(gen, s_gen0 + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
+    return last;
+}
+
+// The exit of a fused launch: the last block to finish reading tells the
+// peers (reduce-op.c:250).
+__device__ __forceinline__ void fused_exit(const SignalFoldArgs &a) {
+    unsigned int *const count = a.gsync;
+    __syncthreads();
+    if (threadIdx.x == 0 &&
+        __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+        __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        peer_handshake(a.sig);
+    }
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
+    // up to 4 elements per lane of one block: the last block to arrive folds
+    // alone, and no block waits for a release or arrives at the exit
+    const bool tiny = a.n <= kFusedTinyElems;
+    static_assert(kFusedTinyElems == (size_t)4 * kBlock, "the tiny case is 4 elements per lane of one block");
+    unsigned int gen0;
+    // a tiny array is folded by the last block alone: the others have fenced
+    // and arrived, and leave
+    if (!fused_entry(a, !tiny, &gen0) && tiny) return;
     T *out = static_cast<T *>(a.out);
     if (tiny) {
         for (size_t i = threadIdx.x; i < a.n; i += kBlock) out[i] = fold_elem<T, OP>(a, i);
@@ -199,13 +223,7 @@ __global__ __launch_bounds__(kBlock) void signal_fold_kernel(SignalFoldArgs a) {
     }
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
     for (size_t i = tid; i < a.n; i += nthr) out[i] = fold_elem<T, OP>(a, i);
-    __syncthreads();
-    // exit: the last block to finish reading tells the peers (reduce-op.c:250)
-    if (threadIdx.x == 0 &&
-        __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-        __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        peer_handshake(a.sig);
-    }
+    fused_exit(a);
 }
 
 // ------------------------------------------------ fused two-shot (SIGNAL)
@@ -359,65 +377,13 @@ __device__ void grid_handshake(const SignalFoldArgs &a, unsigned int gen_now) {
 
 template <typename T, int OP>
 __global__ __launch_bounds__(kBlock) void signal_fold2_kernel(SignalFoldArgs a) {
-    unsigned int *const count = a.gsync, *const gen = a.gsync + 1;
-    __shared__ int s_last;
-    __shared__ unsigned int s_gen0;
-    if (threadIdx.x == 0) {
-        // entry, as the one shot: record the XCD, fence, arrive
-        const unsigned int xcc = (unsigned int)__builtin_amdgcn_s_getreg(kXccIdReg) & 15u;
-        __hip_atomic_store(a.sig.seen + blockIdx.x, kFenceSeen | xcc, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "");   // system scope
-        const unsigned int gen0 = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned int old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (!s_last) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen0) {
-                if (__builtin_amdgcn_s_memrealtime() - t0 > a.sig.timeout_ticks) {
-                    __hip_atomic_store(a.sig.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        s_gen0 = gen0;
-    }
-    __syncthreads();
-    if (s_last && threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        unsigned int rec = 0;
-        if (lane < (int)gridDim.x) {
-            rec = __hip_atomic_load(a.sig.seen + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.sig.seen + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        int covered = 0;
-#pragma unroll
-        for (unsigned int x = 0; x < 16; ++x) covered += __ballot(rec == (kFenceSeen | x)) != 0 ? 1 : 0;
-        if (lane == 0) {
-            atomicAdd(a.sig.fence_stats, 1ull);
-            if (covered < a.sig.nxcc) {
-                atomicAdd(a.sig.fence_stats + 1, 1ull);
-                __hip_atomic_store(a.sig.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            peer_handshake(a.sig);   // reduce-op.c:217: every source is final
-            __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(gen, s_gen0 + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
+    unsigned int gen0;
+    fused_entry(a, true, &gen0);        // every block waits for the entry handshake
     const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
     fold_span<T, OP>(a, tid, nthr);     // my slice from every member's source
-    grid_handshake(a, s_gen0 + 1u);     // every member's slice is final
+    grid_handshake(a, gen0 + 1u);       // every member's slice is final
     gather_span(a, tid, nthr);          // the other slices from the peers' targets
-    __syncthreads();
-    // exit: the last block to finish reading tells the peers (reduce-op.c:250)
-    if (threadIdx.x == 0 &&
-        __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-        __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        peer_handshake(a.sig);
-    }
+    fused_exit(a);
 }
 
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
@@ -432,33 +398,6 @@ hipError_t sf_launch(const SignalFoldArgs &a, hipStream_t s) {
     else
         hipLaunchKernelGGL((signal_fold_kernel<T, OP>), dim3(kFusedBlocks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
-}
-
-template <typename T>
-hipError_t sf_ops(int op, const SignalFoldArgs &a, hipStream_t s) {
-    constexpr bool integral = std::is_integral<T>::value;
-    constexpr bool cplx = std::is_same<T, cplxd>::value || std::is_same<T, cplxf>::value;
-    switch (op) {
-    case SHMEMX_OP_SUM: return sf_launch<T, SHMEMX_OP_SUM>(a, s);
-    case SHMEMX_OP_PROD: return sf_launch<T, SHMEMX_OP_PROD>(a, s);
-    case SHMEMX_OP_AND:
-        if constexpr (integral) return sf_launch<T, SHMEMX_OP_AND>(a, s);
-        break;
-    case SHMEMX_OP_OR:
-        if constexpr (integral) return sf_launch<T, SHMEMX_OP_OR>(a, s);
-        break;
-    case SHMEMX_OP_XOR:
-        if constexpr (integral) return sf_launch<T, SHMEMX_OP_XOR>(a, s);
-        break;
-    case SHMEMX_OP_MIN:
-        if constexpr (!cplx) return sf_launch<T, SHMEMX_OP_MIN>(a, s);
-        break;
-    case SHMEMX_OP_MAX:
-        if constexpr (!cplx) return sf_launch<T, SHMEMX_OP_MAX>(a, s);
-        break;
-    default: break;
-    }
-    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -477,18 +416,11 @@ hipError_t launch_signal_fold(int type, int op, const SignalFoldArgs &a, hipStre
         for (int k = 0; k < a.nseg; ++k)
             if (a.glen[k] && (!a.gsrc[k] || !a.gdst[k])) return hipErrorInvalidValue;
     }
-    switch (type) {
-    case SHMEMX_TYPE_SHORT: return sf_ops<short>(op, a, stream);
-    case SHMEMX_TYPE_INT: return sf_ops<int>(op, a, stream);
-    case SHMEMX_TYPE_LONG:
-    case SHMEMX_TYPE_LONGLONG: return sf_ops<long>(op, a, stream);
-    case SHMEMX_TYPE_FLOAT: return sf_ops<float>(op, a, stream);
-    case SHMEMX_TYPE_DOUBLE: return sf_ops<double>(op, a, stream);
-    case SHMEMX_TYPE_LONGDOUBLE: return sf_ops<ld80>(op, a, stream);
-    case SHMEMX_TYPE_COMPLEXD: return sf_ops<cplxd>(op, a, stream);
-    case SHMEMX_TYPE_COMPLEXF: return sf_ops<cplxf>(op, a, stream);
-    default: return hipErrorInvalidValue;
-    }
+    hipError_t e = hipErrorInvalidValue;
+    with_type_op(type, op, [&](auto t, auto o) {
+        e = sf_launch<typename decltype(t)::type, decltype(o)::value>(a, stream);
+    });
+    return e;
 }
 
 hipError_t launch_signal(const SignalArgs &a, hipStream_t stream) {

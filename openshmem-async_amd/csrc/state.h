@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include "internal.h"
 #include "node.h"
 #include "set_geom.h"
 #include "shmem_reduce_mi355x.h"
@@ -240,7 +241,6 @@ char *ipc_scratch(size_t *bytes);
 // (logged under SHMEM_LOG_LEVELS=info; counted in shmemx_direct_stats).
 void fence_and_wait(hipStream_t s);
 // The device-side fence records and counters the SIGNAL barrier checks.
-struct SignalArgs;   // internal.h
 struct FenceRecords {
     unsigned int *seen;
     int nxcc;
@@ -256,6 +256,19 @@ unsigned long long *loopback_signal_area();
 // signal counters at heap::signal_offset()); false if this PE has no heap
 // segment or a member's segment is not mapped.
 bool signal_args(const ActiveSet &set, SignalArgs *sa);
+// A fused launch (launch_signal_fold) of the P sources ins into out: the one
+// shot as it stands, the two shot after two_shot_args (signal.cpp).
+SignalFoldArgs fused_args(const SignalArgs &sa, void *out, const void *const *ins, int P, size_t n);
+// The fused two shot of member m: fold slice m (set order: fa->ins holds
+// every source in it), then gather the other non-empty slices, ascending,
+// from the members' targets tgt_of(i) into tgt.
+template <class TgtOf>
+void two_shot_args(SignalFoldArgs *fa, const Slices &sl, int m, TgtOf tgt_of, char *tgt) {
+    fa->two_shot = 1;
+    fa->lo = sl.lo(m);
+    fa->hi = sl.hi(m);
+    fa->nseg = gather_segments(sl, m, false, false, tgt_of, tgt, fa->gsrc, fa->gdst, fa->glen);
+}
 // A one-shot reduction as one fused launch (launch_signal_fold): count it in
 // shmemx_direct_stats.
 void count_fused_call();

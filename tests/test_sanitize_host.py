@@ -5,7 +5,8 @@ host barrier and descriptors and the small-call exchange's slot protocol over
 forked PEs (node.cpp), the soft x87
 arithmetic the GPU runs for long double (ld80.h), and the copy threads'
 placement over a fake sysfs tree (topology.cpp), the staging chunk
-schedule (stage_plan.h), the active-set geometry (set_geom.h) and the staging
+schedule (stage_plan.h), the active-set geometry (set_geom.h), the fold
+kernels' 16-byte split and grid (span16.h) and the staging
 copy gang (copy_gang.h, also under ThreadSanitizer).  The same harnesses run
 unsanitized, at larger sizes, in test_heap_host.py, test_node_host.py and
 test_ld80_host.py.  GPU-side sanitizers are not available on the MI355X pool."""
@@ -34,6 +35,8 @@ CASES = {
     "stage_plan": ([os.path.join(NATIVE, "test_stage_plan.cpp")], [], [], "ok "),
     # the active-set geometry of the multi-PE algorithms (set_geom.h)
     "set_geom": ([os.path.join(NATIVE, "test_set_geom.cpp")], [], [], "ok "),
+    # the fold kernels' head / 16-byte body / tail split and their grid (span16.h)
+    "span16": ([os.path.join(NATIVE, "test_span16.cpp")], [], [], "ok "),
     # the copy threads' placement (staging.cpp: cache domains of the GPU's node)
     "topology": ([os.path.join(NATIVE, "test_topology.cpp"), os.path.join(CSRC, "topology.cpp")], [],
                  ["{tmp}/sys"], "ok "),
