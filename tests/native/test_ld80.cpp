@@ -1,6 +1,12 @@
 // Host check of the GPU's x87 soft-float (openshmem-async_amd/csrc/ld80.h)
 // against the host's real x87 unit: add, mul, <, > over random and special
 // 80-bit encodings.  Prints "ok <count>" or the first mismatch and exits 1.
+//
+// test_ld80 --pairs IN OUT: no comparison; IN holds pairs of 16-byte slots
+// (a, b), and OUT receives four slots per pair, the soft add, mul, min and
+// max (a < b ? a : b, a > b ? a : b) of this host build.  A test compares
+// them with the reference, so a pair the GPU build gets wrong can be told
+// apart: host right and device wrong is the compiler, both wrong the logic.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,7 +67,29 @@ static ld80 random_value(int cls) {
     }
 }
 
+static int run_pairs(const char *in_path, const char *out_path) {
+    std::FILE *in = std::fopen(in_path, "rb"), *out = std::fopen(out_path, "wb");
+    if (!in || !out) {
+        std::printf("cannot open %s\n", in ? out_path : in_path);
+        return 2;
+    }
+    ld80 ab[2];
+    long n = 0;
+    while (std::fread(ab, sizeof(ld80), 2, in) == 2) {
+        const ld80 &a = ab[0], &b = ab[1];
+        const ld80 r[4] = {shmx::x87::add(a, b), shmx::x87::mul(a, b), shmx::x87::less(a, b) ? a : b,
+                           shmx::x87::greater(a, b) ? a : b};
+        if (std::fwrite(r, sizeof(ld80), 4, out) != 4) return 2;
+        ++n;
+    }
+    std::fclose(in);
+    if (std::fclose(out) != 0) return 2;
+    std::printf("pairs %ld\n", n);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 4 && std::strcmp(argv[1], "--pairs") == 0) return run_pairs(argv[2], argv[3]);
     const long iters = argc > 1 ? std::atol(argv[1]) : 2000000;
     long checked = 0;
     for (long i = 0; i < iters; ++i) {

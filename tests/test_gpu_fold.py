@@ -12,6 +12,7 @@ Bit-exact for every type/op (floats included: same op order, same IEEE ops).
 import numpy as np
 import pytest
 from gpu_util import from_dev, same_bits, to_dev
+from x87_cases import annex_g_operands
 
 pytestmark = pytest.mark.gpu
 
@@ -157,11 +158,7 @@ def test_fold_special_values_all_pairs(cuda, shm, oracle, t):
 def test_complex_prod_annex_g(cuda, shm, oracle, t):
     """Complex multiply with inf/NaN parts: the __muldc3 recovery branch."""
     import torch
-    ft = np.float64 if t == "complexd" else np.float32
-    parts = np.array([0.0, -0.0, 1.0, -2.0, np.inf, -np.inf, np.nan, 3.5], dtype=ft)
-    zs = np.array([complex(x, y) for x in parts for y in parts],
-                  dtype=np.complex128 if t == "complexd" else np.complex64)
-    a, b = np.repeat(zs, len(zs)), np.tile(zs, len(zs))
+    a, b = annex_g_operands(t)
     want = oracle.reduce_sim(t, "prod", np.stack([a, b]), 0, 0, 2)[0]
     out = torch.empty(len(a), dtype=to_dev(torch, a).dtype, device="cuda")
     shm.fold_n(t, "prod", out, [to_dev(torch, a), to_dev(torch, b)], len(a))

@@ -2,7 +2,9 @@
 same source compiled for the host and compared with the host's x87 unit on
 random and special 80-bit encodings (add, mul, <, >), value bytes exact.
 The GPU build of the same code is checked on the device in
-test_gpu_fold.py::test_longdouble_x87_encodings."""
+test_gpu_fold.py::test_longdouble_x87_encodings; directed operands for every
+rounding path, on the host in test_x87_cases.py and on the device in
+test_gpu_x87_edges.py."""
 import os
 import subprocess
 
