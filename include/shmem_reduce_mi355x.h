@@ -466,6 +466,69 @@ int shmemx_service_fold_loopback(int type, int op, int own_order,
                                  void *dst, void *dst2,
                                  const void *const *srcs, size_t nelems);
 
+/* Test hook: which kernel instance one local fold launch would be, and on
+ * which grid.  Pure host logic: the very argument checks, 16-byte split and
+ * launch choice that the launch itself goes through (one definition each,
+ * csrc/span16.h), from the addresses mod 16 alone.  Nothing is dereferenced
+ * and no HIP call is made, so it needs no device and no shmem_init.
+ *   route   SHMEMX_FOLD_ROUTE_PLAIN   one launch of shmemx_fold_on_stream
+ *                                     (ins = {acc, in}, outs = {acc}) or of
+ *                                     shmemx_fold_n_on_stream; nins == 1 is
+ *                                     the copy;
+ *           SHMEMX_FOLD_ROUTE_PEERS   ... of shmemx_fold_n_peers_on_stream;
+ *           SHMEMX_FOLD_ROUTE_ORDERS  shmemx_fold_orders_on_stream;
+ *   outs    the output (one entry), or the P-order fold's nins outputs;
+ *   ins     the nins inputs.
+ * One launch reads at most 16 inputs (shmemx_fold_n_on_stream chains longer
+ * folds, 16 and then 15 inputs at a time into the output); nins above 16 is
+ * refused here as by the launch.
+ * On OK *shape holds
+ *   family            SHMEMX_FOLD_FAMILY_*: the two-input fold, the fold with
+ *                     a run-time input count, the peers fold, the P-order
+ *                     fold, the copy; SHMEMX_FOLD_FAMILY_NONE (every other
+ *                     field 0) for nelems == 0, which launches nothing;
+ *   maxin             inputs the peers / P-order kernel unrolls (4, 8, 16 /
+ *                     8, 16); 0 for the other families;
+ *   vectors_per_lane  16-byte vectors per input each lane moves in one chunk;
+ *   nt                cache policy bits: 1 non-temporal loads, 2 non-temporal
+ *                     stores (3 from 32 MiB moved, else 0);
+ *   blocks            workgroups (of 256 lanes);
+ *   head, nvec, tail  scalar elements before, 16-byte vectors in, and scalar
+ *                     elements after the vector body (nvec == 0: the arrays
+ *                     differ mod 16 and all nelems are head);
+ *   scalar_trips      trips of the grid-stride loop over the scalar elements,
+ *                     ceil((head + tail) / (blocks * 256));
+ *   ld80_pipelined    the call runs the software-pipelined long double branch
+ *                     (long double, run-time input count, nins >= 3, at
+ *                     least one whole chunk of vectors).
+ * EINVAL exactly where the launch refuses: a pair the reference lacks (for
+ * the P-order fold: any but its six pairs), a route outside 0..2, nins outside
+ * 1..16, NULL shape or outs, a NULL output (the P-order fold: with
+ * nelems > 0), NULL ins or a NULL input with nelems > 0 (the P-order fold:
+ * NULL ins with any nelems). */
+#define SHMEMX_FOLD_ROUTE_PLAIN 0
+#define SHMEMX_FOLD_ROUTE_PEERS 1
+#define SHMEMX_FOLD_ROUTE_ORDERS 2
+#define SHMEMX_FOLD_FAMILY_NONE (-1)
+#define SHMEMX_FOLD_FAMILY_FOLD2 0
+#define SHMEMX_FOLD_FAMILY_FOLD_N 1
+#define SHMEMX_FOLD_FAMILY_PEERS 2
+#define SHMEMX_FOLD_FAMILY_ORDERS 3
+#define SHMEMX_FOLD_FAMILY_COPY 4
+typedef struct {
+    int family;
+    int maxin;
+    int vectors_per_lane;
+    int nt;
+    int ld80_pipelined;
+    long long blocks;
+    long long head, nvec, tail;
+    long long scalar_trips;
+} shmemx_fold_launch_shape_t;
+int shmemx_fold_launch_shape(int type, int op, int route, int nins, size_t nelems,
+                             void *const *outs, const void *const *ins,
+                             shmemx_fold_launch_shape_t *shape);
+
 int shmemx_kernel_timing(int on);
 int shmemx_kernel_times(double *us, int *kind, int max, unsigned long long *dropped);
 

@@ -282,11 +282,8 @@ __global__ __launch_bounds__(kBlock) void fold_kernel(FoldArgs args) {
     signal_host_done(args);
 }
 
-// 16-B vectors per lane per input for the runtime-nins kernel, and for the
-// two-input fold (2 and 8 measured no faster at 32-64 Mi elements:
-// DESIGN_history.md §4.2).
-constexpr int kUnrollN = 4;
-constexpr int kUnrollFold2 = 4;
+// (kUnrollN and kUnrollFold2, the vectors per lane per input of the two
+// kernels above, are span16.h's, with every other number of the launch choice.)
 
 // The P-input fold over inputs that live in the peers' HBM (DIRECT's and
 // SIGNAL's fold phase).  The runtime-nins kernel above issues input k + 1's
@@ -300,8 +297,7 @@ constexpr int kUnrollFold2 = 4;
 // kept 16 vectors (2 per input at 8 inputs); at P = 8 x 16 Mi doubles on
 // local HBM 4 per input runs 201.0 against 204.2 us, 1 per input 345 us
 // (tools/peers_gather_lab.hip, profiles/r03_peers_gather_lab.txt).  The fold
-// order is unchanged: input 0, then 1, ...
-constexpr int peers_unroll(int maxin) { return maxin <= 8 ? 4 : 2; }
+// order is unchanged: input 0, then 1, ...  (peers_unroll: span16.h.)
 
 template <typename T, int OP, int MAXIN, int NT>
 __global__ __launch_bounds__(kBlock) void fold_peers_kernel(FoldArgs args) {
@@ -384,8 +380,7 @@ __global__ __launch_bounds__(kBlock) void fold_peers_kernel(FoldArgs args) {
 // P^2 times would be far past the instruction cache: it takes a ROLLED loop
 // over the orders, whose first input is picked by a chain of uniform selects
 // (x[k] with a run-time k would put the inputs in scratch): 82 VGPRs at
-// MAXIN 8, 148 at 16, no scratch.
-constexpr int kUnrollOrders = 1;
+// MAXIN 8, 148 at 16, no scratch.  (kUnrollOrders = 1: span16.h.)
 
 struct OrdersArgs {
     void *outs[kMaxFoldInputs];
@@ -463,11 +458,10 @@ __global__ __launch_bounds__(kBlock) void fold_orders_kernel(OrdersArgs args) {
 }
 
 
-// The grid of a launch over args (FoldArgs or OrdersArgs): span16.h's rule.
-template <typename Args>
-size_t grid_for(const Args &a, int unroll) {
-    return span_blocks(Span16{a.head, a.nvec, a.tail}, unroll);
-}
+// The launchers below take the LaunchChoice (span16.h) that dispatch() and
+// launch_fold_orders() made for the call and switch on it: which instance
+// runs, on which grid, is decided there and nowhere else, and
+// fold_launch_shape() reports the same choice.
 
 // The marker after the work: the stream's own value write (the command
 // processor stores the word once everything before it on the stream has
@@ -484,66 +478,46 @@ hipError_t enqueue_marker(unsigned long long *word, unsigned long long value, hi
 }
 
 template <typename T, int OP, int NT>
-hipError_t launch_typed_grid(const FoldArgs &a, hipStream_t stream);
+hipError_t launch_typed_grid(const FoldArgs &a, const LaunchChoice &c, hipStream_t stream);
 
 // A fold whose grid is not one workgroup cannot signal from inside (no
 // arrival counter): it runs without, and the marker kernel follows it.
 template <typename T, int OP, int NT>
-hipError_t launch_typed(const FoldArgs &a0, hipStream_t stream) {
-    if (!a0.sig_word) return launch_typed_grid<T, OP, NT>(a0, stream);
-    // the grid launch_typed_grid will use (fold_kernel in every case but
-    // the peers kernel, which never signals)
-    const int u = a0.nins != 2 ? kUnrollN : kUnrollFold2;
-    if (!a0.peers && grid_for(a0, u) == 1) return launch_typed_grid<T, OP, NT>(a0, stream);
+hipError_t launch_typed(const FoldArgs &a0, const LaunchChoice &c, hipStream_t stream) {
+    if (!a0.sig_word) return launch_typed_grid<T, OP, NT>(a0, c, stream);
+    // (a call of the peers route never signals)
+    if (!a0.peers && c.blocks == 1) return launch_typed_grid<T, OP, NT>(a0, c, stream);
     FoldArgs a = a0;
     a.sig_word = nullptr;
-    const hipError_t e = launch_typed_grid<T, OP, NT>(a, stream);
+    const hipError_t e = launch_typed_grid<T, OP, NT>(a, c, stream);
     if (e != hipSuccess) return e;
     return enqueue_marker(a0.sig_word, a0.sig_value, stream);
 }
 
 template <typename T, int OP, int NT>
-hipError_t launch_typed_grid(const FoldArgs &a, hipStream_t stream) {
-    if (a.nins == 2) {
+hipError_t launch_typed_grid(const FoldArgs &a, const LaunchChoice &c, hipStream_t stream) {
+    const dim3 grid((unsigned)c.blocks);
+    if (c.family == kFamilyFold2) {
         // the two-input fold (reduce-op.c:231-235): the hot kernel
-        launch_k(kKindFold, fold_kernel<T, OP, 2, kUnrollFold2, NT>, dim3((unsigned)grid_for(a, kUnrollFold2)),
-                 dim3(kBlock), stream, a);
-    } else if (a.peers && !kHeavyOp<T, OP>) {
-        if (a.nins <= 4)
-            launch_k(kKindPeers, fold_peers_kernel<T, OP, 4, NT>,
-                     dim3((unsigned)grid_for(a, peers_unroll(4))), dim3(kBlock), stream, a);
-        else if (a.nins <= 8)
-            launch_k(kKindPeers, fold_peers_kernel<T, OP, 8, NT>,
-                     dim3((unsigned)grid_for(a, peers_unroll(8))), dim3(kBlock), stream, a);
+        launch_k(kKindFold, fold_kernel<T, OP, 2, kUnrollFold2, NT>, grid, dim3(kBlock), stream, a);
+    } else if (c.family == kFamilyPeers) {
+        if (c.maxin == 4)
+            launch_k(kKindPeers, fold_peers_kernel<T, OP, 4, NT>, grid, dim3(kBlock), stream, a);
+        else if (c.maxin == 8)
+            launch_k(kKindPeers, fold_peers_kernel<T, OP, 8, NT>, grid, dim3(kBlock), stream, a);
         else
-            launch_k(kKindPeers, fold_peers_kernel<T, OP, 16, NT>,
-                     dim3((unsigned)grid_for(a, peers_unroll(16))), dim3(kBlock), stream, a);
+            launch_k(kKindPeers, fold_peers_kernel<T, OP, 16, NT>, grid, dim3(kBlock), stream, a);
     } else {
-        launch_k(kKindFold, fold_kernel<T, OP, 0, kUnrollN, NT>, dim3((unsigned)grid_for(a, kUnrollN)),
-                 dim3(kBlock), stream, a);
+        launch_k(kKindFold, fold_kernel<T, OP, 0, kUnrollN, NT>, grid, dim3(kBlock), stream, a);
     }
     return hipGetLastError();
 }
 
-// Cache policy: working sets of 32 MiB and more go non-temporal on both
-// loads and stores.  Round 1 set the cut at the 256 MiB Infinity Cache from
-// back-to-back (warm) runs; round 3 measured the 4-64 Mi-float fold cold
-// (tools/cold_midsize_probe.py, profiles/r03_cold_midsize.txt): after a
-// producer's writes leave dirty lines in the MALL, the default policy runs
-// 3.1 / 4.1 TB/s at 48 / 192 MiB against 4.3 / 5.8 non-temporal (the
-// default's stores evict those lines and pay their write-back); from a clean
-// cache the default leads by 5-7 %, back to back the two tie.  So
-// non-temporal, whose worst case is the better one, from 32 MiB up; below
-// it a call is launch-bound and the default keeps L2/MALL hits.  (Loads or
-// stores alone non-temporal, and the sc0/sc1 bits, measured no better:
-// profiles/r03_policy_lab*.txt.)
-constexpr size_t kNtThresholdBytes = size_t(32) << 20;
-
+// Cache policy (span16.h nt_policy, kNtThresholdBytes): the choice's nt picks
+// the instance with non-temporal loads and stores.
 template <typename T, int OP>
-hipError_t launch_nt(const FoldArgs &a, hipStream_t stream) {
-    const size_t n = a.head + a.nvec * (16 / sizeof(T)) + a.tail;
-    return (size_t)(a.nins + 1) * n * sizeof(T) >= kNtThresholdBytes ? launch_typed<T, OP, 3>(a, stream)
-                                                                      : launch_typed<T, OP, 0>(a, stream);
+hipError_t launch_nt(const FoldArgs &a, const LaunchChoice &c, hipStream_t stream) {
+    return c.nt ? launch_typed<T, OP, kNtBoth>(a, c, stream) : launch_typed<T, OP, 0>(a, c, stream);
 }
 
 // The copy (nins == 1: reduce-op.c:213-216, the whole PE_size = 1 call, and
@@ -566,22 +540,19 @@ hipError_t launch_nt(const FoldArgs &a, hipStream_t stream) {
 // up to 256 MiB dirty in the Infinity Cache for the next kernel to write back
 // (4.9-5.2 TB/s charged), so the stores stay non-temporal.  kUnrollCopy,
 // kUnrollCopyLarge and the choice between them are span16.h's (copy_small,
-// copy_blocks), which copy_one_workgroup evaluates too.
+// copy_blocks, copy_choice), which copy_one_workgroup evaluates too.
 template <typename T, int NT>
-hipError_t launch_copy_nt(const FoldArgs &a0, hipStream_t stream) {
-    const Span16 span{a0.head, a0.nvec, a0.tail};
-    const bool small = copy_small(span);
-    const size_t blocks = copy_blocks(span);
+hipError_t launch_copy_nt(const FoldArgs &a0, const LaunchChoice &c, hipStream_t stream) {
     // a one-workgroup copy stores the host signal itself (launch_fold_signal);
     // a larger grid is followed by the marker kernel
-    const bool self_signal = a0.sig_word && blocks == 1;
+    const bool self_signal = a0.sig_word && c.blocks == 1;
     FoldArgs a = a0;
     if (!self_signal) a.sig_word = nullptr;
-    if (small)
-        launch_k(kKindCopy, fold_kernel<T, SHMEMX_OP_SUM, 1, kUnrollCopy, NT>, dim3((unsigned)blocks), dim3(kBlock),
-                 stream, a);
+    if (c.unroll == kUnrollCopy)
+        launch_k(kKindCopy, fold_kernel<T, SHMEMX_OP_SUM, 1, kUnrollCopy, NT>, dim3((unsigned)c.blocks),
+                 dim3(kBlock), stream, a);
     else
-        launch_k(kKindCopy, fold_kernel<T, SHMEMX_OP_SUM, 1, kUnrollCopyLarge, NT>, dim3((unsigned)blocks),
+        launch_k(kKindCopy, fold_kernel<T, SHMEMX_OP_SUM, 1, kUnrollCopyLarge, NT>, dim3((unsigned)c.blocks),
                  dim3(kBlock), stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a0.sig_word || self_signal) return e;
@@ -589,10 +560,8 @@ hipError_t launch_copy_nt(const FoldArgs &a0, hipStream_t stream) {
 }
 
 template <typename T>
-hipError_t launch_copy(const FoldArgs &a, hipStream_t stream) {
-    const size_t n = a.head + a.nvec * (16 / sizeof(T)) + a.tail;
-    return 2 * n * sizeof(T) >= kNtThresholdBytes ? launch_copy_nt<T, 3>(a, stream)
-                                                  : launch_copy_nt<T, 0>(a, stream);
+hipError_t launch_copy(const FoldArgs &a, const LaunchChoice &c, hipStream_t stream) {
+    return c.nt ? launch_copy_nt<T, kNtBoth>(a, c, stream) : launch_copy_nt<T, 0>(a, c, stream);
 }
 
 }  // namespace
@@ -623,8 +592,10 @@ namespace {
 
 // Split a's n elements into scalar head, 16-B vector body and scalar tail
 // over every array of the call (split16; a copy's second destination too:
-// the vector body needs all of them on one alignment), then dispatch on type.
-hipError_t dispatch(int type, int op, FoldArgs &a, size_t n, hipStream_t stream) {
+// the vector body needs all of them on one alignment), and choose the
+// instance and the grid for it (span16.h copy_choice / fold_choice).  False
+// for a pair the table lacks.
+bool choose_fold(int type, int op, FoldArgs &a, size_t n, LaunchChoice *c) {
     const size_t sz = type_size(type);
     const void *ptrs[kMaxFoldInputs + 2];
     int nptrs = 0;
@@ -636,37 +607,69 @@ hipError_t dispatch(int type, int op, FoldArgs &a, size_t n, hipStream_t stream)
     a.nvec = span.nvec;
     a.tail = span.tail;
     if (a.nins == 1) {   // a copy: bits only, one kernel per element size
-        switch (sz) {
-        case 2: return launch_copy<short>(a, stream);
-        case 4: return launch_copy<int>(a, stream);
-        case 8: return launch_copy<long>(a, stream);
-        case 16: return launch_copy<cplxd>(a, stream);
-        default: return hipErrorInvalidValue;
+        if (sz != 2 && sz != 4 && sz != 8 && sz != 16) return false;
+        *c = copy_choice(span, sz);
+        return true;
+    }
+    return with_type_op(type, op, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        *c = fold_choice(span, sizeof(T), a.nins, a.peers != 0, kHeavyOp<T, decltype(o)::value>);
+    });
+}
+
+// a's span and the choice made for it, then dispatch on type.
+hipError_t dispatch(int type, int op, FoldArgs &a, size_t n, hipStream_t stream) {
+    LaunchChoice c{};
+    if (!choose_fold(type, op, a, n, &c)) return hipErrorInvalidValue;
+    if (c.family == kFamilyCopy) {
+        switch (type_size(type)) {
+        case 2: return launch_copy<short>(a, c, stream);
+        case 4: return launch_copy<int>(a, c, stream);
+        case 8: return launch_copy<long>(a, c, stream);
+        default: return launch_copy<cplxd>(a, c, stream);
         }
     }
     hipError_t e = hipErrorInvalidValue;
     with_type_op(type, op, [&](auto t, auto o) {
-        e = launch_nt<typename decltype(t)::type, decltype(o)::value>(a, stream);
+        e = launch_nt<typename decltype(t)::type, decltype(o)::value>(a, c, stream);
     });
     return e;
+}
+
+// What a call's arguments amount to: refused, nothing to do (no elements),
+// or a launch.
+enum CallCheck { kCallRefused, kCallNothing, kCallLaunch };
+
+// One fold launch's arguments checked and its FoldArgs filled in (the span
+// is choose_fold's).
+CallCheck fold_call(int type, int op, void *out, const void *const *ins, int nins, size_t n, int peers,
+                    FoldArgs *a) {
+    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out) return kCallRefused;
+    if (n == 0) return kCallNothing;
+    if (!ins) return kCallRefused;
+    *a = FoldArgs{};
+    a->out = out;
+    a->nins = nins;
+    a->peers = peers;
+    for (int k = 0; k < nins; ++k) {
+        if (!ins[k]) return kCallRefused;
+        a->ins[k] = ins[k];
+    }
+    return kCallLaunch;
 }
 
 // launch_fold, launch_fold_signal (sig.word set) and launch_fold_peers: the
 // call checked, its FoldArgs filled in, dispatched.
 hipError_t launch_fold_args(int type, int op, void *out, const void *const *ins, int nins, size_t n, int peers,
                             const HostSignal &sig, hipStream_t stream) {
-    if (!op_on_device(type, op) || nins < 1 || nins > kMaxFoldInputs || !out) return hipErrorInvalidValue;
-    if (n == 0) return sig.word ? launch_host_signal(sig, stream) : hipSuccess;
     FoldArgs a{};
-    a.out = out;
-    a.nins = nins;
-    a.peers = peers;
+    switch (fold_call(type, op, out, ins, nins, n, peers, &a)) {
+    case kCallRefused: return hipErrorInvalidValue;
+    case kCallNothing: return sig.word ? launch_host_signal(sig, stream) : hipSuccess;
+    default: break;
+    }
     a.sig_word = sig.word;
     a.sig_value = sig.value;
-    for (int k = 0; k < nins; ++k) {
-        if (!ins[k]) return hipErrorInvalidValue;
-        a.ins[k] = ins[k];
-    }
     return dispatch(type, op, a, n, stream);
 }
 
@@ -718,57 +721,113 @@ hipError_t launch_fold_peers(int type, int op, void *out, const void *const *ins
 namespace {
 
 template <typename T, int OP, int MAXIN, int NT>
-void launch_orders_grid(const OrdersArgs &a, hipStream_t stream) {
-    launch_k(kKindOrders, fold_orders_kernel<T, OP, MAXIN, NT>,
-             dim3((unsigned)grid_for(a, kUnrollOrders)), dim3(kBlock), stream, a);
+void launch_orders_grid(const OrdersArgs &a, const LaunchChoice &c, hipStream_t stream) {
+    launch_k(kKindOrders, fold_orders_kernel<T, OP, MAXIN, NT>, dim3((unsigned)c.blocks), dim3(kBlock), stream, a);
 }
 
 // P reads and P writes of n elements: non-temporal from 32 MiB moved, as the
-// other folds (kNtThresholdBytes)
+// other folds (span16.h orders_choice)
 template <typename T, int OP>
-hipError_t launch_orders_typed(const OrdersArgs &a, size_t n, hipStream_t stream) {
-    const bool nt = (size_t)(2 * a.nins) * n * sizeof(T) >= kNtThresholdBytes;
-    if (a.nins <= 8) {
-        if (nt) launch_orders_grid<T, OP, 8, 3>(a, stream);
-        else launch_orders_grid<T, OP, 8, 0>(a, stream);
+hipError_t launch_orders_typed(const OrdersArgs &a, const LaunchChoice &c, hipStream_t stream) {
+    if (c.maxin == 8) {
+        if (c.nt) launch_orders_grid<T, OP, 8, kNtBoth>(a, c, stream);
+        else launch_orders_grid<T, OP, 8, 0>(a, c, stream);
     } else {
-        if (nt) launch_orders_grid<T, OP, 16, 3>(a, stream);
-        else launch_orders_grid<T, OP, 16, 0>(a, stream);
+        if (c.nt) launch_orders_grid<T, OP, 16, kNtBoth>(a, c, stream);
+        else launch_orders_grid<T, OP, 16, 0>(a, c, stream);
     }
     return hipGetLastError();
+}
+
+// the pairs whose answer depends on the order (own_order_pair)
+template <typename T, int OP>
+constexpr bool kOwnOrderPair = (std::is_same<T, float>::value || std::is_same<T, double>::value ||
+                                std::is_same<T, ld80>::value) &&
+                               (OP == SHMEMX_OP_MIN || OP == SHMEMX_OP_MAX);
+
+// The P-order fold's arguments checked, its OrdersArgs filled in, the span
+// over all 2 P arrays (the vector body only if they share one alignment) and
+// the choice for it.
+CallCheck orders_call(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
+                      OrdersArgs *a, LaunchChoice *c) {
+    if ((op != SHMEMX_OP_MIN && op != SHMEMX_OP_MAX) || nins < 1 || nins > kMaxFoldInputs || !outs || !ins)
+        return kCallRefused;
+    if (n == 0) return kCallNothing;
+    *a = OrdersArgs{};
+    a->nins = nins;
+    const void *ptrs[2 * kMaxFoldInputs];
+    for (int k = 0; k < nins; ++k) {
+        if (!ins[k] || !outs[k]) return kCallRefused;
+        ptrs[2 * k] = a->ins[k] = ins[k];
+        ptrs[2 * k + 1] = a->outs[k] = outs[k];
+    }
+    const Span16 span = split16(ptrs, 2 * nins, type_size(type), n);
+    a->head = span.head;
+    a->nvec = span.nvec;
+    a->tail = span.tail;
+    bool own = false;
+    with_type_op(type, op, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        if constexpr (kOwnOrderPair<T, decltype(o)::value>) {
+            own = true;
+            *c = orders_choice(span, sizeof(T), nins);
+        }
+    });
+    return own ? kCallLaunch : kCallRefused;
 }
 
 }  // namespace
 
 hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
                               hipStream_t stream) {
-    if ((op != SHMEMX_OP_MIN && op != SHMEMX_OP_MAX) || nins < 1 || nins > kMaxFoldInputs || !outs || !ins)
-        return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
     OrdersArgs a{};
-    a.nins = nins;
-    const void *ptrs[2 * kMaxFoldInputs];
-    for (int k = 0; k < nins; ++k) {
-        if (!ins[k] || !outs[k]) return hipErrorInvalidValue;
-        ptrs[2 * k] = a.ins[k] = ins[k];
-        ptrs[2 * k + 1] = a.outs[k] = outs[k];
+    LaunchChoice c{};
+    switch (orders_call(type, op, outs, ins, nins, n, &a, &c)) {
+    case kCallRefused: return hipErrorInvalidValue;
+    case kCallNothing: return hipSuccess;
+    default: break;
     }
-    // the vector body only if all 2 P arrays share one alignment
-    const Span16 span = split16(ptrs, 2 * nins, type_size(type), n);
-    a.head = span.head;
-    a.nvec = span.nvec;
-    a.tail = span.tail;
     hipError_t e = hipErrorInvalidValue;
     with_type_op(type, op, [&](auto t, auto o) {
         using T = typename decltype(t)::type;
         constexpr int OP = decltype(o)::value;
-        // the pairs whose answer depends on the order (own_order_pair)
-        if constexpr ((std::is_same<T, float>::value || std::is_same<T, double>::value ||
-                       std::is_same<T, ld80>::value) &&
-                      (OP == SHMEMX_OP_MIN || OP == SHMEMX_OP_MAX))
-            e = launch_orders_typed<T, OP>(a, n, stream);
+        if constexpr (kOwnOrderPair<T, OP>) e = launch_orders_typed<T, OP>(a, c, stream);
     });
     return e;
+}
+
+// ------------------------------------------------- the launch-shape query
+// What launch_fold (route 0), launch_fold_peers (1) or launch_fold_orders (2)
+// would launch for these arguments: the very checks, split and choice the
+// launches go through (fold_call + choose_fold, orders_call), with no HIP
+// call and no access to the arrays.  outs: the output (one entry) or, for
+// the P-order fold, the nins outputs.
+bool fold_launch_shape(int type, int op, int route, void *const *outs, const void *const *ins, int nins, size_t n,
+                       FoldLaunchShape *shape) {
+    *shape = FoldLaunchShape{};
+    CallCheck call = kCallRefused;
+    if (route == kRouteOrders) {
+        OrdersArgs a{};
+        call = orders_call(type, op, outs, ins, nins, n, &a, &shape->choice);
+        shape->span = Span16{a.head, a.nvec, a.tail};
+    } else if ((route == kRoutePlain || route == kRoutePeers) && outs) {
+        FoldArgs a{};
+        call = fold_call(type, op, outs[0], ins, nins, n, route == kRoutePeers, &a);
+        if (call == kCallLaunch && !choose_fold(type, op, a, n, &shape->choice)) call = kCallRefused;
+        shape->span = Span16{a.head, a.nvec, a.tail};
+    }
+    if (call == kCallRefused) return false;
+    shape->launches = call == kCallLaunch;
+    if (!shape->launches) {
+        *shape = FoldLaunchShape{};
+        return true;
+    }
+    shape->scalar_trips = scalar_trips(shape->span, shape->choice.blocks);
+    // fold_body's software-pipelined branch: long double through the
+    // runtime-nins kernel with three inputs or more, in the whole chunks
+    shape->ld80_pipelined = type == SHMEMX_TYPE_LONGDOUBLE && shape->choice.family == kFamilyFoldN && nins >= 3 &&
+                            shape->span.nvec >= (size_t)kBlock * shape->choice.unroll;
+    return true;
 }
 
 // ------------------------------------------------------------ gather copy

@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "span16.h"   // Span16, LaunchChoice
+
 namespace shmx {
 
 // Upper bound on inputs one fold launch reads; longer folds are chained
@@ -74,6 +76,24 @@ hipError_t launch_fold_peers(int type, int op, void *out, const void *const *ins
 // and long double min / max only).  outs[k] may be ins[k]; no other overlap.
 hipError_t launch_fold_orders(int type, int op, void *const *outs, const void *const *ins, int nins, size_t n,
                               hipStream_t stream);
+
+// What one of the three launches above would launch (shmemx_fold_launch_shape):
+// route 0 launch_fold, 1 launch_fold_peers, 2 launch_fold_orders; outs is
+// the one output, or the P-order fold's nins outputs.  The same checks,
+// 16-byte split and choice (span16.h LaunchChoice) as the launch itself, from
+// the addresses mod 16 alone: no HIP call, nothing dereferenced.  False where
+// the launch would refuse the arguments; launches == false (and all else
+// zero) where it would have nothing to do (n == 0).
+enum FoldRoute { kRoutePlain = 0, kRoutePeers = 1, kRouteOrders = 2 };
+struct FoldLaunchShape {
+    bool launches;
+    LaunchChoice choice;
+    Span16 span;
+    size_t scalar_trips;    // trips of the grid-stride loop over head + tail
+    bool ld80_pipelined;    // fold_body's long double branch for nins >= 3
+};
+bool fold_launch_shape(int type, int op, int route, void *const *outs, const void *const *ins, int nins, size_t n,
+                       FoldLaunchShape *shape);
 
 // Copy nseg (<= kMaxFoldInputs) byte ranges srcs[i] -> dsts[i] in one launch
 // (DIRECT all-gather: the peers' result slices, read concurrently).

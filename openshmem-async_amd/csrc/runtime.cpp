@@ -1238,6 +1238,34 @@ int shmemx_reduce_plan(int type, int op, int nreduce, int PE_start,
     return make_plan(type, op, nreduce, PE_start, logPE_stride, PE_size, pe, npes, algo, plan);
 }
 
+// Host logic only (fold_kernels.hip fold_launch_shape): no device, no lock,
+// no error state.
+int shmemx_fold_launch_shape(int type, int op, int route, int nins, size_t nelems, void *const *outs,
+                             const void *const *ins, shmemx_fold_launch_shape_t *shape) {
+    static_assert(SHMEMX_FOLD_ROUTE_PLAIN == kRoutePlain && SHMEMX_FOLD_ROUTE_PEERS == kRoutePeers &&
+                      SHMEMX_FOLD_ROUTE_ORDERS == kRouteOrders && SHMEMX_FOLD_FAMILY_FOLD2 == kFamilyFold2 &&
+                      SHMEMX_FOLD_FAMILY_FOLD_N == kFamilyFoldN && SHMEMX_FOLD_FAMILY_PEERS == kFamilyPeers &&
+                      SHMEMX_FOLD_FAMILY_ORDERS == kFamilyOrders && SHMEMX_FOLD_FAMILY_COPY == kFamilyCopy,
+                  "the header's numbers are span16.h's and internal.h's");
+    if (!shape) return SHMEMX_EINVAL;
+    FoldLaunchShape s{};
+    if (!fold_launch_shape(type, op, route, outs, ins, nins, nelems, &s)) return SHMEMX_EINVAL;
+    *shape = shmemx_fold_launch_shape_t{};
+    shape->family = SHMEMX_FOLD_FAMILY_NONE;
+    if (!s.launches) return SHMEMX_OK;
+    shape->family = s.choice.family;
+    shape->maxin = s.choice.maxin;
+    shape->vectors_per_lane = s.choice.unroll;
+    shape->nt = s.choice.nt;
+    shape->ld80_pipelined = s.ld80_pipelined ? 1 : 0;
+    shape->blocks = (long long)s.choice.blocks;
+    shape->head = (long long)s.span.head;
+    shape->nvec = (long long)s.span.nvec;
+    shape->tail = (long long)s.span.tail;
+    shape->scalar_trips = (long long)s.scalar_trips;
+    return SHMEMX_OK;
+}
+
 long shmemx_set_fused_twoshot_kb(long kb) {
     if (kb < 0) {
         set_error(SHMEMX_EINVAL);

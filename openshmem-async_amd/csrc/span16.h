@@ -1,7 +1,9 @@
 // How the fold-family kernels (fold_kernels.hip) cut n elements into a scalar
-// head, a body of 16-byte vectors and a scalar tail, and how many workgroups
-// such a launch takes.  The staging path (copy_one_workgroup) relies on the
-// launch and its own forecast agreeing, so each rule has one definition here.
+// head, a body of 16-byte vectors and a scalar tail, how many workgroups such
+// a launch takes, and which kernel instance it is: family, inputs unrolled,
+// vectors per lane, cache policy.  The staging path (copy_one_workgroup) and
+// the launch-shape query (shmemx_fold_launch_shape) rely on the launch and
+// their own forecast agreeing, so each rule has one definition here.
 // Header-only and host-only, so tests/native/test_span16.cpp checks it on the
 // CPU.
 #pragma once
@@ -55,6 +57,111 @@ constexpr int kUnrollCopyLarge = 1;
 inline bool copy_small(const Span16 &s) { return s.nvec <= (size_t)kBlock * kUnrollCopy; }
 inline size_t copy_blocks(const Span16 &s) {
     return span_blocks(s, copy_small(s) ? kUnrollCopy : kUnrollCopyLarge);
+}
+
+// ------------------------------------------------------------ cache policy
+// Working sets of 32 MiB and more go non-temporal on both loads and stores.
+// Round 1 set the cut at the 256 MiB Infinity Cache from back-to-back (warm)
+// runs; round 3 measured the 4-64 Mi-float fold cold
+// (tools/cold_midsize_probe.py, profiles/r03_cold_midsize.txt): after a
+// producer's writes leave dirty lines in the MALL, the default policy runs
+// 3.1 / 4.1 TB/s at 48 / 192 MiB against 4.3 / 5.8 non-temporal (the
+// default's stores evict those lines and pay their write-back); from a clean
+// cache the default leads by 5-7 %, back to back the two tie.  So
+// non-temporal, whose worst case is the better one, from 32 MiB up; below
+// it a call is launch-bound and the default keeps L2/MALL hits.  (Loads or
+// stores alone non-temporal, and the sc0/sc1 bits, measured no better:
+// profiles/r03_policy_lab*.txt.)
+// `arrays` is how many arrays of n elements the call moves: nins + 1 for a
+// fold (its inputs and its output), 2 for the copy, 2 nins for the P-order
+// fold (P reads, P writes).
+constexpr size_t kNtThresholdBytes = size_t(32) << 20;
+constexpr int kNtBoth = 3;   // fold_ops.h ld16 / st16: bit 0 loads, bit 1 stores
+inline bool nt_policy(size_t arrays, size_t n, size_t elem_size) {
+    return arrays * n * elem_size >= kNtThresholdBytes;
+}
+
+// ----------------------------------------------------------- launch choice
+// Which kernel instance a call launches, and its grid.  The launchers of
+// fold_kernels.hip switch on a LaunchChoice and nothing else, and
+// shmemx_fold_launch_shape reports the same one, so what the tests are told
+// was launched is what was launched.
+enum FoldFamily {
+    kFamilyFold2 = 0,    // fold_kernel<T, OP, 2, kUnrollFold2, NT>
+    kFamilyFoldN = 1,    // fold_kernel<T, OP, 0, kUnrollN, NT>: run-time input count
+    kFamilyPeers = 2,    // fold_peers_kernel<T, OP, MAXIN, NT>
+    kFamilyOrders = 3,   // fold_orders_kernel<T, OP, MAXIN, NT>
+    kFamilyCopy = 4,     // fold_kernel<T, SUM, 1, kUnrollCopy | kUnrollCopyLarge, NT>
+};
+struct LaunchChoice {
+    int family;      // FoldFamily
+    int maxin;       // inputs unrolled at compile time (peers, orders); else 0
+    int unroll;      // 16-byte vectors per lane per input in a chunk
+    int nt;          // 0, or kNtBoth
+    size_t blocks;   // the grid
+};
+
+// 16-B vectors per lane per input for the runtime-nins kernel, and for the
+// two-input fold (2 and 8 measured no faster at 32-64 Mi elements:
+// DESIGN_history.md §4.2); for the peers kernels 4 up to 8 inputs (32
+// vectors in registers), 2 up to 16; one for the P-order fold
+// (fold_kernels.hip has the measurements behind each).
+constexpr int kUnrollN = 4;
+constexpr int kUnrollFold2 = 4;
+constexpr int peers_unroll(int maxin) { return maxin <= 8 ? 4 : 2; }
+constexpr int kUnrollOrders = 1;
+
+inline size_t span_elems(const Span16 &s, size_t elem_size) { return s.head + s.nvec * (16 / elem_size) + s.tail; }
+
+// A fold of nins >= 2 inputs.  Two inputs: the two-input kernel, whatever the
+// route.  More, on the peers route: the peers kernel for up to 4, 8 or 16
+// inputs, except for a heavy pair (fold_ops.h kHeavyOp: long double and the
+// complex products), which keeps the runtime-nins kernel as every fold of
+// the plain route does.
+inline LaunchChoice fold_choice(const Span16 &s, size_t elem_size, int nins, bool peers, bool heavy) {
+    LaunchChoice c{};
+    if (nins == 2) {
+        c.family = kFamilyFold2;
+        c.unroll = kUnrollFold2;
+    } else if (peers && !heavy) {
+        c.family = kFamilyPeers;
+        c.maxin = nins <= 4 ? 4 : nins <= 8 ? 8 : 16;
+        c.unroll = peers_unroll(c.maxin);
+    } else {
+        c.family = kFamilyFoldN;
+        c.unroll = kUnrollN;
+    }
+    c.nt = nt_policy((size_t)nins + 1, span_elems(s, elem_size), elem_size) ? kNtBoth : 0;
+    c.blocks = span_blocks(s, c.unroll);
+    return c;
+}
+
+// The copy (one input).
+inline LaunchChoice copy_choice(const Span16 &s, size_t elem_size) {
+    LaunchChoice c{};
+    c.family = kFamilyCopy;
+    c.unroll = copy_small(s) ? kUnrollCopy : kUnrollCopyLarge;
+    c.nt = nt_policy(2, span_elems(s, elem_size), elem_size) ? kNtBoth : 0;
+    c.blocks = copy_blocks(s);
+    return c;
+}
+
+// The P-order fold: nins inputs, nins outputs.
+inline LaunchChoice orders_choice(const Span16 &s, size_t elem_size, int nins) {
+    LaunchChoice c{};
+    c.family = kFamilyOrders;
+    c.maxin = nins <= 8 ? 8 : 16;
+    c.unroll = kUnrollOrders;
+    c.nt = nt_policy(2 * (size_t)nins, span_elems(s, elem_size), elem_size) ? kNtBoth : 0;
+    c.blocks = span_blocks(s, c.unroll);
+    return c;
+}
+
+// Trips of the kernels' grid-stride loop over the scalar head and tail
+// (for_scalar_edges): the whole array when the operands differ mod 16.
+inline size_t scalar_trips(const Span16 &s, size_t blocks) {
+    const size_t nthr = blocks * kBlock;
+    return nthr ? (s.head + s.tail + nthr - 1) / nthr : 0;
 }
 
 }  // namespace shmx

@@ -51,6 +51,14 @@ class Plan(ctypes.Structure):
                 ("tail", ctypes.c_longlong), ("ws_bytes", ctypes.c_longlong)]
 
 
+class LaunchShape(ctypes.Structure):
+    _fields_ = [("family", ctypes.c_int), ("maxin", ctypes.c_int),
+                ("vectors_per_lane", ctypes.c_int), ("nt", ctypes.c_int),
+                ("ld80_pipelined", ctypes.c_int), ("blocks", ctypes.c_longlong),
+                ("head", ctypes.c_longlong), ("nvec", ctypes.c_longlong),
+                ("tail", ctypes.c_longlong), ("scalar_trips", ctypes.c_longlong)]
+
+
 _lib = None
 
 
@@ -121,6 +129,9 @@ def lib() -> ctypes.CDLL:
     L.shmemx_fused_loopback.restype = i
     L.shmemx_reduce_plan.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(Plan)]
     L.shmemx_reduce_plan.restype = i
+    L.shmemx_fold_launch_shape.argtypes = [i, i, i, i, sz, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                           ctypes.POINTER(LaunchShape)]
+    L.shmemx_fold_launch_shape.restype = i
     L.shmemx_get_uniqueid.argtypes = [vp]
     L.shmemx_get_uniqueid.restype = i
     L.shmemx_uniqueid_size.restype = i
@@ -388,6 +399,43 @@ def plan(type_name: str, op: str, nreduce: int, PE_start: int, logPE_stride: int
     inv = {v: k for k, v in ALGOS.items()}
     return PlanInfo(inv[p.algo], p.member, p.nmembers, p.elem_size, p.chunk, p.main,
                     p.tail, p.ws_bytes)
+
+
+FOLD_ROUTES = {"plain": 0, "peers": 1, "orders": 2}
+FOLD_FAMILIES = {-1: None, 0: "fold2", 1: "fold_n", 2: "peers", 3: "orders", 4: "copy"}
+
+
+@dataclass
+class LaunchShapeInfo:
+    family: str | None      # None: nothing is launched (nelems == 0)
+    maxin: int
+    vectors_per_lane: int
+    nt: int
+    blocks: int
+    head: int
+    nvec: int
+    tail: int
+    scalar_trips: int
+    ld80_pipelined: bool
+
+
+def fold_launch_shape(type_name: str, op: str, route: str, outs, ins, nelems: int) -> LaunchShapeInfo:
+    """shmemx_fold_launch_shape: the kernel instance and grid that
+    fold / fold_n (route "plain"; one input: the copy), fold_n(peers=True)
+    ("peers") or fold_orders_on_stream ("orders") would launch for these
+    arrays, which may be plain integer addresses: only their values mod 16
+    are looked at.  outs: the output, or the list of "orders" outputs.
+    Host logic only; no GPU needed."""
+    if not isinstance(outs, (list, tuple)):
+        outs = [outs]
+    a = (ctypes.c_void_p * max(len(outs), 1))(*[addr(x) for x in outs])
+    b = (ctypes.c_void_p * max(len(ins), 1))(*[addr(x) for x in ins])
+    s = LaunchShape()
+    rc = lib().shmemx_fold_launch_shape(TYPES[type_name], OPS[op], FOLD_ROUTES[route], len(ins), nelems,
+                                        a, b, ctypes.byref(s))
+    _check(rc, f"shmemx_fold_launch_shape({type_name},{op},{route},nins={len(ins)})")
+    return LaunchShapeInfo(FOLD_FAMILIES[s.family], s.maxin, s.vectors_per_lane, s.nt, s.blocks, s.head,
+                           s.nvec, s.tail, s.scalar_trips, bool(s.ld80_pipelined))
 
 
 def rccl_register_heap(on: bool) -> None:

@@ -310,6 +310,75 @@ def test_fold_n_argument_errors_without_a_device(shm, peers):
     assert fn(T["double"], O["sum"], 8, ins, 2, 0, None) == 0             # zero elements
 
 
+def test_fold_launch_shape_is_declared_exported_and_host_only(shm):
+    """shmemx_fold_launch_shape: the header declares it, nm -D shows it as a
+    defined function, and it answers from the addresses mod 16 alone (made-up
+    addresses, no device): family, MAXIN, vectors per lane, NT bits, grid,
+    split, scalar trips.  EINVAL exactly where the launch refuses."""
+    import ctypes
+    assert "shmemx_fold_launch_shape" in declared_functions()
+    assert exported()["shmemx_fold_launch_shape"][1] == "T"
+    q = shm.fold_launch_shape
+    A = [0x7F0000000000 + (k << 32) for k in range(17)]
+    n2 = (32 << 20) // 24                                  # 3 arrays of n doubles reach 32 MiB one past this
+    s = q("double", "sum", "plain", A[0], [A[0], A[1]], n2 + 1)
+    assert (s.family, s.maxin, s.vectors_per_lane, s.nt) == ("fold2", 0, 4, 3)
+    assert (s.head, s.nvec, s.tail, s.scalar_trips) == (0, (n2 + 1) // 2, (n2 + 1) % 2, (n2 + 1) % 2)
+    assert s.blocks == -(-s.nvec // 1024) and not s.ld80_pipelined
+    assert q("double", "sum", "plain", A[0], [A[0], A[1]], n2).nt == 0
+    s = q("short", "max", "peers", A[0] + 2, [a + 2 for a in A[1:6]], 1000)
+    assert (s.family, s.maxin, s.vectors_per_lane, s.nt, s.blocks) == ("peers", 8, 4, 0, 1)
+    assert (s.head, s.nvec, s.tail, s.scalar_trips) == (7, 124, 1, 1)
+    s = q("short", "max", "peers", A[0], [a + 2 for a in A[1:6]], 2048 * 256 + 1)   # the target apart
+    assert (s.family, s.head, s.nvec, s.tail, s.blocks, s.scalar_trips) == ("peers", 2048 * 256 + 1, 0, 0, 2048, 2)
+    assert q("int", "xor", "peers", A[0], A[1:13], 4096).maxin == 16
+    assert q("int", "xor", "peers", A[0], A[1:13], 4096).vectors_per_lane == 2
+    assert q("int", "xor", "peers", A[0], A[1:3], 4096).family == "fold2"
+    assert q("int", "xor", "plain", A[0], A[1:13], 4096).family == "fold_n"
+    s = q("longdouble", "prod", "peers", A[0], A[1:4], 4096)         # heavy: the runtime-nins kernel
+    assert (s.family, s.maxin, s.ld80_pipelined) == ("fold_n", 0, True)
+    assert not q("longdouble", "prod", "plain", A[0], A[1:4], 1023).ld80_pipelined   # no whole chunk
+    assert q("complexf", "prod", "peers", A[0], A[1:4], 64).family == "fold_n"
+    assert q("complexf", "sum", "peers", A[0], A[1:4], 64).family == "peers"
+    s = q("float", "min", "orders", A[:9], A[8:17], 1000)             # outs[8] is ins[0]: addresses only
+    assert (s.family, s.maxin, s.vectors_per_lane, s.nvec) == ("orders", 16, 1, 250)
+    assert q("float", "min", "orders", A[:8], A[8:16], 1000).maxin == 8
+    s = q("complexd", "sum", "plain", A[0], [A[1] + 8], 300)          # the copy, source at 8 mod 16
+    assert (s.family, s.vectors_per_lane, s.nvec, s.blocks, s.scalar_trips) == ("copy", 8, 0, 2, 1)
+    assert q("int", "sum", "plain", A[0], [A[1]], 2048 * 4).vectors_per_lane == 8
+    assert q("int", "sum", "plain", A[0], [A[1]], 2048 * 4 + 4).vectors_per_lane == 1
+    s = q("int", "sum", "plain", A[0], [A[1]], 0)                     # nothing to launch
+    assert s.family is None and s.blocks == 0
+
+    fn = shm.lib().shmemx_fold_launch_shape
+    T, O = shm.TYPES, shm.OPS
+    out = shm.LaunchShape()
+    good = (ctypes.c_void_p * 17)(*A)
+    hole = (ctypes.c_void_p * 17)(*(A[:3] + [None] + A[4:]))
+    null_out = (ctypes.c_void_p * 1)(None)
+
+    def call(t="double", op="sum", route=0, nins=3, n=64, outs=good, ins=good, shape=out):
+        return fn(T[t], O[op], route, nins, n, outs, ins, ctypes.byref(shape) if shape is not None else None)
+
+    assert call() == 0
+    assert call(op="xor") == 1                        # not a reference pair
+    assert fn(99, 0, 0, 3, 64, good, good, ctypes.byref(out)) == 1
+    for route in (-1, 3):
+        assert call(route=route) == 1
+    for route in (0, 1, 2):
+        op = "max" if route == 2 else "sum"
+        assert call(op=op, route=route, nins=0) == 1 and call(op=op, route=route, nins=17) == 1
+        assert call(op=op, route=route, nins=16) == 0
+        assert call(op=op, route=route, nins=5, ins=hole) == 1     # a NULL input
+        assert call(op=op, route=route, outs=None) == 1
+        assert call(op=op, route=route, ins=None) == 1
+        assert call(op=op, route=route, shape=None) == 1
+    assert call(outs=null_out) == 1 and call(route=1, outs=null_out) == 1
+    assert call(route=2, op="max", nins=5, outs=hole) == 1          # a NULL output of the P-order fold
+    assert call(route=2, op="sum") == 1 and call(route=2, t="int", op="max") == 1   # not an own-order pair
+    assert call(n=0, ins=None) == 0 and out.family == -1            # zero elements: the inputs are not looked at
+
+
 def test_fused_loopback_argument_errors_without_a_device(shm):
     """shmemx_fused_loopback rejects bad arguments before touching HIP: EINVAL
     for a pair the reference lacks, a schedule outside 0..2, P outside 1..16,

@@ -279,21 +279,29 @@ def test_copy_moves_bits_every_size_offset_and_nt_path(cuda, shm, t):
     bytes, NaN payloads and long double padding included, come out identical,
     at every element offset mod 16 (the scalar head and tail), for lengths
     around one workgroup's chunk, and above the 32 MiB non-temporal cut; the
-    bytes around the target are untouched."""
+    bytes around the target are untouched.  Source and target share their
+    address mod 16 at the odd lengths and differ at the even ones; the large
+    length runs once each way (long double, whose C alignment is 16, only
+    aligned; double _Complex differs by its 8)."""
     import torch
     sz = shm.type_size(t)
     rng = np.random.default_rng(hash(t) & 0xFFFF)
     chunk = 256 * 8 * 16 // sz              # one workgroup: 256 lanes x 8 vectors
     lens = [1, 3, chunk - 1, chunk, chunk + 1, 3 * chunk + 7, (17 << 20) // sz + 5]
     for n in lens:
-        for off in range(0, 16, sz) if n < 1 << 20 else (0, 16 - sz if sz < 16 else 0):
-            src = torch.from_numpy(rng.integers(0, 256, n * sz + 64, dtype=np.uint8)).cuda()
-            dst = torch.full((n * sz + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-            s_off = off if n % 2 else (off + sz) % 16   # same / different alignment mod 16
-            shm.fold_n(t, "sum", dst[off:off + n * sz], [src[s_off:s_off + n * sz]], n)
-            torch.cuda.synchronize()
-            assert torch.equal(dst[off:off + n * sz], src[s_off:s_off + n * sz]), (t, n, off, s_off)
-            assert bool((dst[:off] == 0xA5).all()) and bool((dst[off + n * sz:] == 0xA5).all()), (t, n, off)
+        large = n >= 1 << 20
+        for off in (0, 16 - sz if sz < 16 else 0) if large else range(0, 16, sz):
+            s_offs = [off if n % 2 else (off + sz) % 16]   # same / different alignment mod 16
+            if large and t != "longdouble":
+                s_offs.append((off + min(sz, 8)) % 16)     # the large length both ways
+            for s_off in s_offs:
+                src = torch.from_numpy(rng.integers(0, 256, n * sz + 64, dtype=np.uint8)).cuda()
+                dst = torch.full((n * sz + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+                shm.fold_n(t, "sum", dst[off:off + n * sz], [src[s_off:s_off + n * sz]], n)
+                torch.cuda.synchronize()
+                assert torch.equal(dst[off:off + n * sz], src[s_off:s_off + n * sz]), (t, n, off, s_off)
+                assert bool((dst[:off] == 0xA5).all()) and bool((dst[off + n * sz:] == 0xA5).all()), (t, n, off)
+    assert n % 2 == 1 and large, "the large length is odd: aligned alike by the parity rule"
 
 
 def _dev_bytes(torch, a, lead=0):
