@@ -232,6 +232,20 @@ enum {
  *           launch.  A peer that never arrives
  *           times out after $SHMEMX_SIGNAL_TIMEOUT s (default 20); the next
  *           blocking call then aborts with a FATAL line.
+ *           Own slice, opt-in ($SHMEMX_SIGNAL_OWNSLICE=1, every PE alike, or
+ *           shmemx_set_signal_ownslice; default off): the six own-order pairs
+ *           (below) above $SHMEMX_DIRECT_ONESHOT_KB run OWNSLICE's schedule
+ *           under SIGNAL's device barriers instead of every member reading
+ *           every whole source: member m folds slice m of every source in
+ *           all P orders, its own into its target and the others into slots
+ *           in the second half of its IPC scratch region
+ *           ($SHMEMX_DIRECT_SCRATCH_MB), device barrier, every member copies
+ *           its slot from every other owner.  2(P-1)/P of the array per PE
+ *           instead of (P-1)x, stream-ordered and capturable (after one warm
+ *           call of the set, which allocates, maps and votes on the scratch
+ *           regions); exact in place needs no temporary.  One fused launch
+ *           per chunk up to $SHMEMX_FUSED_TWOSHOT_KB, five launches above;
+ *           a call whose slots exceed half the scratch runs in chunks.
  *   OWNSLICE  opt-in, for the six own-order pairs (below) at two-shot cost:
  *           member m reads slice m of every member's source (as DIRECT's
  *           first phase) and folds it in all P orders at once, one result
@@ -255,7 +269,8 @@ enum {
  * each PE its own reference answer (reduce-op.c:130-142, 219-248), so on
  * these six pairs every algorithm folds in the calling PE's own order: A2A
  * runs as GATHER, DIRECT and SIGNAL read every member's whole source;
- * OWNSLICE has each slice's owner fold it in every member's order. */
+ * OWNSLICE (and SIGNAL with its own slice on) has each slice's owner fold
+ * it in every member's order. */
 enum {
     SHMEMX_ALGO_AUTO = 0, SHMEMX_ALGO_RCCL, SHMEMX_ALGO_A2A,
     SHMEMX_ALGO_GATHER, SHMEMX_ALGO_ALLREDUCE, SHMEMX_ALGO_DIRECT, SHMEMX_ALGO_SIGNAL,
@@ -547,6 +562,44 @@ int shmemx_set_comms(void);
  * EINVAL) for kb < 0. */
 long shmemx_set_fused_twoshot_kb(long kb);
 
+/* SIGNAL's own slice (the SIGNAL paragraph above): on != 0 turns it on, 0
+ * off (default $SHMEMX_SIGNAL_OWNSLICE, else off).  Every member of a set
+ * must hold the same value when it calls.  Returns the previous value (0 or
+ * 1), or -1 (and EINVAL) for on < 0.  With it on, shmemx_reduce_plan reports
+ * the slice as chunk and the P - 1 result slots as ws_bytes for the calls
+ * that take it; shmemx_direct_stats counts them in [14] and [15]. */
+long shmemx_set_signal_ownslice(long on);
+
+/* Bytes of one member's result slots in OWNSLICE's and SIGNAL's own-slice
+ * schedules for nelems elements of `type` over P members: P - 1 slots of one
+ * slice (ceil(nelems / P) elements rounded up to 16 bytes) each.  Host logic
+ * only.  0 for an unknown type or P outside 1..16. */
+size_t shmemx_order_slots_bytes(int type, int P, size_t nelems);
+
+/* Test hook: SIGNAL's fused own-slice launch on one GPU, with no heap and no
+ * peers, as shmemx_fused_loopback runs the other fused launches (the same
+ * looped-back handshakes, 2 s bound, shared device-side barrier state and
+ * device handling).  Runs member m's launch of a P-member set whose sources
+ * srcs[i], targets tgts[i] and slot areas slots[i]
+ * (shmemx_order_slots_bytes(type, P, nelems) bytes each) are all device
+ * arrays of the calling process, and waits for it.  With [lo(i), hi(i)) the
+ * two-shot slices of nelems over P: m folds elements [lo(m), hi(m)) of every
+ * source in every member's own order (k first, then the others ascending),
+ * order m into tgts[m] there and order k != m into slots[m] at slot
+ * (k < m ? k : k - 1), slots of one whole slice each; then it copies, for
+ * every other owner i of a non-empty slice, slot (m < i ? m : m - 1) of
+ * slots[i] to tgts[m][lo(i), hi(i)).  tgts[i] may be srcs[i] exactly.
+ * *signal_error as for shmemx_fused_loopback.  Returns OK (at once for
+ * nelems == 0); EDEVICE for a failed launch or a non-zero error word; before
+ * any HIP call, EINVAL for a pair the reference lacks, P outside 1..16, m
+ * outside 0..P-1 or, with nelems > 0, NULL tgts / srcs / slots or a NULL
+ * entry (slots' entries may be NULL for P == 1), and ENOTSUP for a reference
+ * pair outside the six. */
+int shmemx_fused_orders_loopback(int type, int op, int P, int m,
+                                 void *const *tgts, const void *const *srcs,
+                                 void *const *slots, size_t nelems,
+                                 unsigned int *signal_error, void *stream);
+
 /* How a call would be executed (pure host logic, no device needed). */
 typedef struct {
     int algo;          /* resolved SHMEMX_ALGO_* (never AUTO)               */
@@ -626,7 +679,9 @@ int shmemx_mirror_stats(unsigned long long *out, int nout, int reset);
  * calls (DIRECT or SIGNAL) that ran as one fused launch, [12] two-shot calls
  * that did ($SHMEMX_FUSED_TWOSHOT_KB, default 4096), [13] calls that ran
  * OWNSLICE's two-phase schedule (its phases are timed in [3]-[6]: the P-order
- * fold as the fold, the pull of the result slots as the gather).  Fills at most
+ * fold as the fold, the pull of the result slots as the gather), [14] SIGNAL
+ * calls that ran its own slice, [15] those of them whose every chunk was one
+ * fused launch.  Fills at most
  * nout values and returns how many; reset != 0 zeroes the counters. */
 int shmemx_direct_stats(double *out, int nout, int reset);
 

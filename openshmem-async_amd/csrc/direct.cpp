@@ -123,6 +123,8 @@ double g_calls;
 double g_fused_calls;   // one-shot calls that ran as one fused launch (DIRECT and SIGNAL)
 double g_fused2_calls;  // two-shot calls that ran as one fused launch
 double g_ownslice_calls;  // calls that ran OWNSLICE's two-phase schedule
+double g_signal_ownslice_calls;        // SIGNAL calls that ran it under device barriers
+double g_signal_ownslice_fused_calls;  // ... each chunk as one fused launch
 
 double now_us() {
     return std::chrono::duration<double, std::micro>(
@@ -137,13 +139,13 @@ double now_us() {
 // of them alike; the combinations that passed are remembered, and every
 // member decides identically whether to vote (same set, same regions, same
 // generations from the shared block).
-bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set) {
+bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set, bool local_ok) {
     uint64_t key = 1469598103934665603ull;
     auto mix = [&key](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
     mix((uint64_t)set.start);
     mix((uint64_t)set.step);
     mix((uint64_t)set.size);
-    bool ok = true;
+    bool ok = local_ok;
     for (const auto &rp : regs) {
         mix((uint64_t)rp.first);
         mix((uint64_t)rp.second);
@@ -288,6 +290,10 @@ void node_done(int start, int step, int P, hipStream_t s, double *stream_us, dou
 
 void count_fused_call() { g_fused_calls += 1; }
 void count_fused_twoshot_call() { g_fused2_calls += 1; }
+void count_signal_ownslice_call(bool fused) {
+    g_signal_ownslice_calls += 1;
+    if (fused) g_signal_ownslice_fused_calls += 1;
+}
 
 bool fused_oneshot_enabled() {
     static const bool on = [] {
@@ -349,8 +355,9 @@ bool signal_args(const ActiveSet &set, SignalArgs *sa) {
 int direct_stats(double *out, int nout, bool reset) {
     // [calls, 6 phase times, host fences, host refills, device fence
     // checks, device fences that missed an XCD, fused one-shot calls, fused
-    // two-shot calls, OWNSLICE two-phase calls]
-    double all[1 + kNumPhases + 7] = {g_calls};
+    // two-shot calls, OWNSLICE two-phase calls, SIGNAL own-slice calls, those
+    // of them that ran fused]
+    double all[1 + kNumPhases + 9] = {g_calls};
     for (int i = 0; i < kNumPhases; ++i) all[1 + i] = g_phase_us[i];
     unsigned long long dev[2] = {0, 0};
     if (g_fence.dev_stats) {
@@ -364,6 +371,8 @@ int direct_stats(double *out, int nout, bool reset) {
     all[5 + kNumPhases] = g_fused_calls;
     all[6 + kNumPhases] = g_fused2_calls;
     all[7 + kNumPhases] = g_ownslice_calls;
+    all[8 + kNumPhases] = g_signal_ownslice_calls;
+    all[9 + kNumPhases] = g_signal_ownslice_fused_calls;
     const int k = std::min(nout, (int)(sizeof all / sizeof all[0]));
     for (int i = 0; i < k; ++i) out[i] = all[i];
     if (reset) {
@@ -371,6 +380,7 @@ int direct_stats(double *out, int nout, bool reset) {
         for (double &v : g_phase_us) v = 0;
         g_fence.host_checks = g_fence.host_refills = 0;
         g_fused_calls = g_fused2_calls = g_ownslice_calls = 0;
+        g_signal_ownslice_calls = g_signal_ownslice_fused_calls = 0;
         if (g_fence.dev_stats) SHMX_HIP(hipMemset(g_fence.dev_stats, 0, sizeof dev));
     }
     return k;
@@ -501,8 +511,8 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     // elements per staged chunk: half the scratch; for OWNSLICE what leaves
     // room in the other half for the P - 1 result slots of the chunk's
     // slices (each rounded up to the granule) and their skew of < 16 bytes
-    const size_t room = ownslice ? half - std::min(half, (size_t)16 * (P + 1)) : half;
-    const size_t cmax = std::max(g, (room / sz) / g * g);
+    // (order_chunk_elems, set_geom.h)
+    const size_t cmax = ownslice ? order_chunk_elems(half, P, sz) : std::max(g, (half / sz) / g * g);
     // Small arrays: one shot — every member folds the whole array itself (in
     // set order, so all agree, or each in its own) and writes only its own
     // target: one kernel and two barriers instead of two kernels and three.
@@ -648,6 +658,9 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         // whether or not anybody stages (n is collective)
         chunked |= !single;
         g_ownslice_calls += 1;
+        // the slots serve SIGNAL's own slice too, on any stream: after its
+        // last use, as the workspaces (released below, once the chunks ran)
+        ws_acquire(s);
     }
     const size_t C = chunked ? cmax : std::max<size_t>(n, 1);
     const size_t nchunks = (n + C - 1) / C;
@@ -738,6 +751,7 @@ int direct_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
         // reduce-op.c:250: no member reads my slice any more
         node_done(start, step, P, s, &g_phase_us[kGather], &g_phase_us[kExitBarrier], tg);
     }
+    if (ownslice) ws_release(s);
     if (local_write && stage_tgt) SHMX_HIP(hipStreamSynchronize(s));
     return SHMEMX_OK;
 }

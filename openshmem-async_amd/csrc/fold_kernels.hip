@@ -389,34 +389,8 @@ struct OrdersArgs {
     size_t head, nvec, tail;   // as FoldArgs
 };
 
-// member k's order over the values x[0..nins): x[k], then the others ascending
-template <typename T, int OP, int MAXIN, bool ROLLED, typename V, typename Ap, typename St>
-__device__ __forceinline__ void fold_orders_of(const V (&x)[MAXIN], int nins, Ap ap, St store) {
-    if constexpr (ROLLED) {
-#pragma unroll 1
-        for (int k = 0; k < nins; ++k) {
-            V acc = x[0];
-#pragma unroll
-            for (int j = 1; j < MAXIN; ++j)
-                if (j == k) acc = x[j];
-#pragma unroll
-            for (int j = 0; j < MAXIN; ++j)
-                if (j != k && j < nins) acc = ap(acc, x[j]);
-            store(k, acc);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < MAXIN; ++k) {
-            if (k < nins) {
-                V acc = x[k];
-#pragma unroll
-                for (int j = 0; j < MAXIN; ++j)
-                    if (j != k && j < nins) acc = ap(acc, x[j]);
-                store(k, acc);
-            }
-        }
-    }
-}
+// (fold_orders_of, member k's order over a lane's values: fold_ops.h, shared
+// with the fused SIGNAL form, signal_kernels.hip signal_orders2_kernel.)
 
 template <typename T, int OP, int MAXIN, int NT>
 __global__ __launch_bounds__(kBlock) void fold_orders_kernel(OrdersArgs args) {
@@ -738,12 +712,6 @@ hipError_t launch_orders_typed(const OrdersArgs &a, const LaunchChoice &c, hipSt
     }
     return hipGetLastError();
 }
-
-// the pairs whose answer depends on the order (own_order_pair)
-template <typename T, int OP>
-constexpr bool kOwnOrderPair = (std::is_same<T, float>::value || std::is_same<T, double>::value ||
-                                std::is_same<T, ld80>::value) &&
-                               (OP == SHMEMX_OP_MIN || OP == SHMEMX_OP_MAX);
 
 // The P-order fold's arguments checked, its OrdersArgs filled in, the span
 // over all 2 P arrays (the vector body only if they share one alignment) and

@@ -230,6 +230,44 @@ constexpr bool kHeavyOp = std::is_same<T, ld80>::value ||
                           ((std::is_same<T, cplxd>::value || std::is_same<T, cplxf>::value) &&
                            OP == SHMEMX_OP_PROD);
 
+// ------------------------------------------------------ the P-order fold
+// the pairs whose answer depends on the order (own_order_pair)
+template <typename T, int OP>
+constexpr bool kOwnOrderPair = (std::is_same<T, float>::value || std::is_same<T, double>::value ||
+                                std::is_same<T, ld80>::value) &&
+                               (OP == SHMEMX_OP_MIN || OP == SHMEMX_OP_MAX);
+
+// member k's order over the values x[0..nins): x[k], then the others
+// ascending; for every k, store(k, result).  ROLLED: fold_kernels.hip, above
+// fold_orders_kernel.
+template <typename T, int OP, int MAXIN, bool ROLLED, typename V, typename Ap, typename St>
+__device__ __forceinline__ void fold_orders_of(const V (&x)[MAXIN], int nins, Ap ap, St store) {
+    if constexpr (ROLLED) {
+#pragma unroll 1
+        for (int k = 0; k < nins; ++k) {
+            V acc = x[0];
+#pragma unroll
+            for (int j = 1; j < MAXIN; ++j)
+                if (j == k) acc = x[j];
+#pragma unroll
+            for (int j = 0; j < MAXIN; ++j)
+                if (j != k && j < nins) acc = ap(acc, x[j]);
+            store(k, acc);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < MAXIN; ++k) {
+            if (k < nins) {
+                V acc = x[k];
+#pragma unroll
+                for (int j = 0; j < MAXIN; ++j)
+                    if (j != k && j < nins) acc = ap(acc, x[j]);
+                store(k, acc);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 }  // namespace shmx

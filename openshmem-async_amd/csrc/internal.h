@@ -183,6 +183,24 @@ struct SignalFoldArgs {
 };
 hipError_t launch_signal_fold(int type, int op, const SignalFoldArgs &a, hipStream_t stream);
 
+// SIGNAL's own slice as ONE launch (signal.cpp; the six own-order pairs only):
+// the fused two shot above with the P-order fold in place of the slice fold.
+// After the entry handshake every block folds its share of elements [lo, hi)
+// of the f.nins sources f.ins[k] (set order, indexed as the array) in every
+// member's order at once: order k's result of element lo + i goes to
+// outs[k][i] (outs[me]: slice me of this member's target; the others: its
+// result slots).  outs[k] may be exactly f.ins[k] + lo (in place); no other
+// overlap.  Mid handshake (every owner's slots are final), then the nseg byte
+// ranges f.gsrc[k] -> f.gdst[k] (this member's slot in every other owner's
+// area, gather_order_slots), exit handshake.  f.out is this member's target
+// (checked, not written through); f.two_shot, f.host_word are ignored.  Its
+// own struct, so the kernarg layout of the launches above does not move.
+struct SignalOrdersArgs {
+    SignalFoldArgs f;
+    void *outs[kMaxFoldInputs];
+};
+hipError_t launch_signal_orders(int type, int op, const SignalOrdersArgs &a, hipStream_t stream);
+
 // Position-aware 64-bit checksum of n elements of `type` at device address
 // ptr (16-byte aligned) into out[0], then `epoch` into out[1] (device memory
 // or host-mapped page-locked memory: system-scope stores, in that order),

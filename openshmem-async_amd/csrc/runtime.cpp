@@ -207,7 +207,8 @@ static const char *const kPlanSettings[] = {
     "SHMEM_REDUCE_ALGO",        "SHMEMX_AUTO_FULL",         "SHMEMX_AUTO_PARTIAL",
     "SHMEMX_ALLREDUCE_MAX_KB",  "SHMEMX_DIRECT_ONESHOT_KB", "SHMEMX_FUSED_TWOSHOT_KB",
     "SHMEMX_FUSED_ONESHOT",     "SHMEMX_SET_COMMS",         "SHMEMX_SET_COMMS_MAX",
-    "SHMEMX_STAGE_CHUNK_MB",    "SHMEMX_DIRECT_SCRATCH_MB", "SHMEMX_TRANSPORT"};
+    "SHMEMX_STAGE_CHUNK_MB",    "SHMEMX_DIRECT_SCRATCH_MB", "SHMEMX_TRANSPORT",
+    "SHMEMX_SIGNAL_OWNSLICE"};
 
 static std::string plan_settings() {
     std::string t;
@@ -592,6 +593,11 @@ int make_plan(int type, int op, int nreduce, int start, int logstride, int size,
     case SHMEMX_ALGO_DIRECT:
     case SHMEMX_ALGO_SIGNAL:   // slice per member (own order: all of it); no workspace
         p->chunk = own ? n : (long long)Slices(n, P, sz).slice;
+        // SIGNAL's own slice (opt-in): OWNSLICE's slice and result slots
+        if (algo == SHMEMX_ALGO_SIGNAL && signal_ownslice_route(own, (size_t)(n * sz))) {
+            p->chunk = (long long)Slices(n, P, sz).slice;
+            p->ws_bytes = (long long)(P - 1) * p->chunk * sz;
+        }
         break;
     case SHMEMX_ALGO_OWNSLICE:
         // above the one-shot limit a slice per member and P - 1 result slots

@@ -86,6 +86,16 @@ inline size_t order_slot(const Slices &sl, int owner, int k) {
 }
 inline size_t order_slots_bytes(const Slices &sl) { return (size_t)(sl.P - 1) * sl.slice * sl.elem_size; }
 
+// Elements per chunk of an OWNSLICE call whose result slots live in `half`
+// bytes (half the IPC scratch): the most whose P - 1 slots, each slice rounded
+// up to the granule, and a skew of < 16 bytes (the slots start at the
+// sources' offset mod 16) fit; a whole number of granules, at least one.
+inline size_t order_chunk_elems(size_t half, int P, size_t elem_size) {
+    const size_t g = granule(elem_size);
+    const size_t room = half - std::min(half, (size_t)16 * (P + 1));
+    return std::max(g, (room / elem_size) / g * g);
+}
+
 // The segments member m gathers in OWNSLICE's second phase: from every other
 // owner i of a non-empty slice, m's result slot in i's slot area at
 // slots_of(i), to slice i of tgt; from member m + 1 on, wrapping, as the

@@ -40,10 +40,30 @@
 //   one shot at every size, each member folding src_me first, then the other
 //   members ascending (reduce-op.c:219-248); in place, into the private
 //   temporary, copied over the target after the second barrier.
+// Own slice ($SHMEMX_SIGNAL_OWNSLICE=1 / shmemx_set_signal_ownslice, default
+//   off; the same six pairs above the one-shot limit): OWNSLICE's schedule
+//   (direct.cpp) under these device barriers, so own order at the two shot's
+//   traffic is stream-ordered and capturable too:
+//   barrier                 every source is final; nobody reads my slots
+//   fold in all P orders    slice m of all P sources: my order -> my target's
+//                           slice m, the others -> my result slots
+//   barrier                 every owner's slots are final
+//   gather                  my slot from every other owner -> my target
+//   barrier                 nobody reads my source or my slots any more
+//   — as ONE fused launch per chunk up to $SHMEMX_FUSED_TWOSHOT_KB
+//   (launch_signal_orders), five launches above it.  The slots are the
+//   second half of every PE's IPC scratch region, whose size is a plan
+//   setting, so every member computes every owner's slot addresses itself; a
+//   call whose slots do not fit is cut into chunks, each a whole schedule.
+//   Only its owner writes a target, a slice at a time after the phase that
+//   read it: exact in place needs no temporary, and nothing on this route is
+//   refused on one member alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <set>
+#include <tuple>
 #include <vector>
 
 #include "heap.h"
@@ -101,6 +121,102 @@ SignalFoldArgs fused_args(const SignalArgs &sa, void *out, const void *const *in
     return fa;
 }
 
+namespace {
+
+long signal_ownslice_from_env() {
+    const char *e = std::getenv("SHMEMX_SIGNAL_OWNSLICE");
+    return e && std::atol(e) > 0 ? 1 : 0;
+}
+long g_signal_ownslice = signal_ownslice_from_env();
+
+// the sets that have met the own-slice route (their scratch regions published,
+// mapped and voted on), with the generation of this PE's scratch at the time:
+// after a finalize and a new init every PE publishes again
+std::set<std::tuple<int, int, int, uint64_t>> g_ownslice_met;
+
+// The peers' scratch regions for the own-slice route.  The first time a set
+// meets it every member allocates and publishes its scratch, the members
+// pass one host barrier (so nobody looks for a region before its owner has
+// published it), and only then map and vote: an allocation or a mapping that
+// failed on one member fails the call on all of them alike.  Later calls are
+// plain lookups.  (Under capture the warm call has done this.)
+bool map_slot_areas(const ActiveSet &set, size_t *half) {
+    size_t bytes = 0;
+    const bool have = ipc_scratch(&bytes) != nullptr;
+    const auto key = std::make_tuple(set.start, set.step, set.size, node::region_gen(node::kScratch, g_state.pe));
+    if (!g_ownslice_met.count(key)) node::barrier(set.start, set.step, set.size);
+    std::vector<std::pair<node::Region, int>> regs;
+    for (int i = 0; i < set.size; ++i) regs.emplace_back(node::kScratch, set.pe_of(i));
+    if (!map_regions(regs, set, have)) return false;
+    g_ownslice_met.insert(key);
+    *half = bytes / 2;
+    return true;
+}
+
+// SIGNAL's own slice (the header comment): member m of the set, operands at
+// heap offsets soff / toff, hb the members' heap bases.
+int signal_ownslice(int type, int op, char *tgt, size_t n, size_t sz, const ActiveSet &set, int m,
+                    const SignalArgs &sa, const std::vector<char *> &hb, uint64_t soff, hipStream_t s) {
+    const int P = set.size;
+    size_t half = 0;
+    if (!map_slot_areas(set, &half)) {
+        trace(LOG_REDUCTION, "SIGNAL own slice: a member has no scratch region or could not map a peer's (%s)",
+              node::last_ipc_error());
+        return set_error(SHMEMX_ENOTSUP);
+    }
+    // every owner's slots start at the sources' offset mod 16, so the fold's
+    // 2 P arrays share an alignment whenever the target does (as direct.cpp)
+    const size_t skew = soff & 15u;
+    auto slots_of = [&](int i) { return node::peer_base(node::kScratch, set.pe_of(i)) + half + skew; };
+    const size_t C = std::min(std::max<size_t>(n, 1), order_chunk_elems(half, P, sz));
+    const bool fused = C * sz <= fused_twoshot_bytes();
+    auto barrier = [&] {
+        SHMX_HIP(launch_sys_fence(s, sa.seen));
+        SHMX_HIP(launch_signal(sa, s));
+    };
+    ws_acquire(s);   // the slots serve every stream, and DIRECT's OWNSLICE
+    for (size_t c0 = 0; c0 < n; c0 += C) {
+        const size_t cnt = std::min(C, n - c0);
+        const Slices sl(cnt, P, sz);
+        const size_t lo = sl.lo(m), hi = sl.hi(m);
+        SignalOrdersArgs oa{};
+        const void *ins[kMaxFoldInputs];
+        for (int i = 0; i < P; ++i) {
+            ins[i] = hb[i] + soff + c0 * sz;
+            oa.outs[i] = i == m ? tgt + (c0 + lo) * sz : slots_of(m) + order_slot(sl, m, i);
+        }
+        oa.f = fused_args(sa, tgt, ins, P, cnt);
+        oa.f.lo = lo;
+        oa.f.hi = hi;
+        oa.f.nseg = gather_order_slots(sl, m, slots_of, tgt + c0 * sz, oa.f.gsrc, oa.f.gdst, oa.f.glen);
+        if (fused) {
+            SHMX_HIP(launch_signal_orders(type, op, oa, s));   // reduce-op.c:217-250
+            continue;
+        }
+        barrier();   // reduce-op.c:217
+        if (hi > lo) {
+            for (int i = 0; i < P; ++i) ins[i] = hb[i] + soff + (c0 + lo) * sz;
+            SHMX_HIP(launch_fold_orders(type, op, oa.outs, ins, P, hi - lo, s));
+        }
+        barrier();   // every owner's slots are final
+        SHMX_HIP(launch_gather(oa.f.gsrc, oa.f.gdst, oa.f.glen, oa.f.nseg, s));
+        barrier();   // reduce-op.c:250
+    }
+    ws_release(s);
+    count_signal_ownslice_call(fused);
+    return SHMEMX_OK;
+}
+
+}  // namespace
+
+bool signal_ownslice_enabled() { return g_signal_ownslice != 0; }
+
+long set_signal_ownslice(long on) {
+    const long prev = g_signal_ownslice;
+    g_signal_ownslice = on ? 1 : 0;
+    return prev;
+}
+
 int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int start,
                   int logstride, const shmemx_plan_t &p, bool own_order, hipStream_t s) {
     const int P = p.nmembers, m = p.member;
@@ -126,6 +242,8 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     if (!signal_args(set, &sa)) return set_error(SHMEMX_ENOTSUP);
     std::vector<char *> hb(P);
     for (int i = 0; i < P; ++i) hb[i] = node::peer_base(node::kHeap, set.pe_of(i));
+    if (signal_ownslice_route(own_order && P > 1 && own_order_pair(type, op), bytes))
+        return signal_ownslice(type, op, tgt, n, sz, set, m, sa, hb, soff, s);
     // every whole source, in set order, or in my own (src_me first, then
     // the other members ascending: reduce-op.c:219-248)
     const void *ins[kMaxFoldInputs];
@@ -194,6 +312,30 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
 
 using namespace shmx;
 
+// The looped-back handshakes of the test hooks below: PE 0 of PEs 0..P-1 over
+// the private signal area, where peer[i] + me is the word mine + pe[i] the
+// launch has just bumped.  False if the area cannot be had.
+static bool loopback_signal_args(int P, SignalArgs *sa) {
+    *sa = SignalArgs{};
+    sa->mine = loopback_signal_area();
+    if (!sa->mine) return false;
+    sa->P = P;
+    sa->me = 0;
+    for (int i = 0; i < P; ++i) {
+        sa->pe[i] = i;
+        sa->peer[i] = sa->mine + i;
+    }
+    // a bound, not a tuned number: a broken barrier ends the kernel in
+    // seconds (2 s of the 100 MHz clock), not at $SHMEMX_SIGNAL_TIMEOUT
+    sa->timeout_ticks = 200000000ull;
+    sa->err = signal_error_word();
+    const FenceRecords fr = fence_records();
+    sa->seen = fr.seen;
+    sa->nxcc = fr.nxcc;
+    sa->fence_stats = fr.stats;
+    return true;
+}
+
 // Test hook: member m's launch of a P-member set whose members' arrays all
 // belong to this process, with the peer handshakes looped back onto the
 // launch's own counters (peer[i] + me is the word mine + pe[i] it has just
@@ -217,22 +359,7 @@ extern "C" int shmemx_fused_loopback(int type, int op, int schedule, int P, int 
     const LocalDevice dev(stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
     SignalArgs sa{};
-    sa.mine = loopback_signal_area();
-    if (!sa.mine) return set_error(SHMEMX_ENOMEM);
-    sa.P = P;
-    sa.me = 0;
-    for (int i = 0; i < P; ++i) {
-        sa.pe[i] = i;
-        sa.peer[i] = sa.mine + i;
-    }
-    // a bound, not a tuned number: a broken barrier ends the kernel in
-    // seconds (2 s of the 100 MHz clock), not at $SHMEMX_SIGNAL_TIMEOUT
-    sa.timeout_ticks = 200000000ull;
-    sa.err = signal_error_word();
-    const FenceRecords fr = fence_records();
-    sa.seen = fr.seen;
-    sa.nxcc = fr.nxcc;
-    sa.fence_stats = fr.stats;
+    if (!loopback_signal_args(P, &sa)) return set_error(SHMEMX_ENOMEM);
     hipError_t e = hipSuccess;
     HostSignal sig{nullptr, 0};
     if (schedule == 2) {
@@ -262,4 +389,61 @@ extern "C" int shmemx_fused_loopback(int type, int op, int schedule, int P, int 
     if (sig.word && *static_cast<volatile unsigned long long *>(sig.word) != sig.value)
         return set_error(SHMEMX_EDEVICE);
     return SHMEMX_OK;
+}
+
+// Test hook: member m's fused own-slice launch (launch_signal_orders, set up
+// as signal_ownslice sets it up) of a P-member set whose members' sources,
+// targets and slot areas all belong to this process; the handshakes looped
+// back as above.
+extern "C" int shmemx_fused_orders_loopback(int type, int op, int P, int m, void *const *tgts,
+                                            const void *const *srcs, void *const *slots, size_t nelems,
+                                            unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!op_valid(type, op) || P < 1 || P > kMaxFoldInputs || m < 0 || m >= P) return set_error(SHMEMX_EINVAL);
+    if (!own_order_pair(type, op)) return set_error(SHMEMX_ENOTSUP);
+    if (nelems == 0) return SHMEMX_OK;
+    if (!tgts || !srcs || !slots) return set_error(SHMEMX_EINVAL);
+    for (int i = 0; i < P; ++i)
+        if (!tgts[i] || !srcs[i] || (P > 1 && !slots[i])) return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalArgs sa{};
+    if (!loopback_signal_args(P, &sa)) return set_error(SHMEMX_ENOMEM);
+    const size_t sz = type_size(type);
+    const Slices sl(nelems, P, sz);
+    char *const tgt = static_cast<char *>(tgts[m]);
+    auto slots_of = [&](int i) { return static_cast<char *>(slots[i]); };
+    SignalOrdersArgs oa{};
+    oa.f = fused_args(sa, tgt, srcs, P, nelems);
+    oa.f.lo = sl.lo(m);
+    oa.f.hi = sl.hi(m);
+    for (int i = 0; i < P; ++i)
+        oa.outs[i] = i == m ? tgt + sl.lo(m) * sz : slots_of(m) + order_slot(sl, m, i);
+    oa.f.nseg = gather_order_slots(sl, m, slots_of, tgt, oa.f.gsrc, oa.f.gdst, oa.f.glen);
+    hipError_t e = launch_signal_orders(type, op, oa, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}
+
+// Host only: the bytes of one member's result slots for an array of nelems
+// elements over P members (set_geom.h order_slots_bytes); 0 for an unknown
+// type or P outside 1..16.
+extern "C" size_t shmemx_order_slots_bytes(int type, int P, size_t nelems) {
+    const size_t sz = type_size(type);
+    if (!sz || P < 1 || P > kMaxFoldInputs) return 0;
+    return order_slots_bytes(Slices(nelems, P, sz));
+}
+
+extern "C" long shmemx_set_signal_ownslice(long on) {
+    if (on < 0) {
+        set_error(SHMEMX_EINVAL);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return set_signal_ownslice(on);
 }

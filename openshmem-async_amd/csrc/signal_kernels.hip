@@ -386,6 +386,82 @@ __global__ __launch_bounds__(kBlock) void signal_fold2_kernel(SignalFoldArgs a) 
     fused_exit(a);
 }
 
+// ------------------------------------------- fused own slice (SIGNAL)
+// The fused two shot for the six own-order pairs: the owner of a slice folds
+// it in all P member orders at once (fold_orders_of, fold_ops.h), its own
+// order into its target's slice, the other P - 1 into its result slots; after
+// the mid handshake every member gathers its slot from every other owner.
+//
+// The fold is fold_orders_kernel's vector body (fold_kernels.hip, whose
+// measured table says why): ONE 16-byte vector per input per lane, all nins
+// loads of a vector issued back to back under the one guard v < nvec before
+// the first select and before any store (so outs[k] may be ins[k] + lo: the
+// in-place call), MAXIN 8 / 16, the rolled order loop for long double.
+// Non-temporal loads, plain stores, as fold_vecs.  The vector body runs only
+// when all P inputs at lo and all P outputs are 16-byte aligned; otherwise
+// the scalar loop takes the whole slice, as fold_span decides.
+//
+// Both MAXIN bodies are in one kernel, so its registers are the MAXIN 16
+// body's.  hipcc (ROCm 7), gfx950, -O3, per instance: VGPRs / AGPRs / SGPRs /
+// scratch bytes per lane / waves per SIMD
+//     float        min, max   151 / 0 / 106 / 0 / 3
+//     double       min, max   151 / 0 / 106 / 0 / 3
+//     long double  min        150 / 0 / 106 / 0 / 3
+//     long double  max        147 / 0 / 106 / 0 / 3
+// No instance touches scratch memory.  The 2 P array pointers and the gather's
+// 3 x 16 words are all wave-uniform, more than the SGPR file: 38 SGPRs (float,
+// double) and 364 (long double, around the rolled loop's soft-x87 compare)
+// are parked in VGPR lanes (v_writelane / v_readlane), which the VGPR counts
+// above include.
+template <typename T, int OP, int MAXIN>
+__device__ __forceinline__ void orders_span_of(const SignalOrdersArgs &a, bool vec, size_t tid, size_t nthr) {
+    constexpr int E = 16 / sizeof(T);
+    constexpr bool ROLLED = std::is_same<T, ld80>::value;
+    const int nins = a.f.nins;
+    const size_t lo = a.f.lo, n = a.f.hi - a.f.lo;
+    const size_t nvec = vec ? n / E : 0;
+    auto in = [&](int k) { return reinterpret_cast<const u32x4 *>(static_cast<const T *>(a.f.ins[k]) + lo); };
+    for (size_t v = tid; v < nvec; v += nthr) {
+        u32x4 x[MAXIN];
+#pragma unroll
+        for (int k = 0; k < MAXIN; ++k)
+            if (k < nins) x[k] = __builtin_nontemporal_load(in(k) + v);
+        fold_orders_of<T, OP, MAXIN, ROLLED>(
+            x, nins, [](u32x4 p, u32x4 q) { return apply16<T, OP>(p, q); },
+            [&](int k, u32x4 r) { static_cast<u32x4 *>(a.outs[k])[v] = r; });
+    }
+    for (size_t i = nvec * E + tid; i < n; i += nthr) {
+        T x[MAXIN];
+#pragma unroll
+        for (int k = 0; k < MAXIN; ++k)
+            if (k < nins) x[k] = static_cast<const T *>(a.f.ins[k])[lo + i];
+        fold_orders_of<T, OP, MAXIN, ROLLED>(
+            x, nins, [](T p, T q) { return Op<T, OP>::ap(p, q); },
+            [&](int k, T r) { static_cast<T *>(a.outs[k])[i] = r; });
+    }
+}
+
+template <typename T, int OP>
+__device__ __forceinline__ void orders_span(const SignalOrdersArgs &a, size_t tid, size_t nthr) {
+    bool vec = true;
+    for (int k = 0; k < a.f.nins; ++k)
+        vec &= ((reinterpret_cast<uintptr_t>(static_cast<const T *>(a.f.ins[k]) + a.f.lo) |
+                 reinterpret_cast<uintptr_t>(a.outs[k])) & 15) == 0;
+    if (a.f.nins <= 8) orders_span_of<T, OP, 8>(a, vec, tid, nthr);
+    else orders_span_of<T, OP, 16>(a, vec, tid, nthr);
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(kBlock) void signal_orders2_kernel(SignalOrdersArgs a) {
+    unsigned int gen0;
+    fused_entry(a.f, true, &gen0);        // every block waits for the entry handshake
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
+    orders_span<T, OP>(a, tid, nthr);     // my slice of every source, in every member's order
+    grid_handshake(a.f, gen0 + 1u);       // every owner's slots are final
+    gather_span(a.f, tid, nthr);          // my slot of every other owner's slice
+    fused_exit(a.f);
+}
+
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
 // check counts them); 8-32 blocks measured within 1 us of it
 // (profiles/r05_fused_blocks.txt).
@@ -419,6 +495,30 @@ hipError_t launch_signal_fold(int type, int op, const SignalFoldArgs &a, hipStre
     hipError_t e = hipErrorInvalidValue;
     with_type_op(type, op, [&](auto t, auto o) {
         e = sf_launch<typename decltype(t)::type, decltype(o)::value>(a, stream);
+    });
+    return e;
+}
+
+hipError_t launch_signal_orders(int type, int op, const SignalOrdersArgs &a, hipStream_t stream) {
+    const SignalFoldArgs &f = a.f;
+    if (f.nins < 1 || f.nins > kMaxFoldInputs || !f.out || !f.gsync || !f.sig.seen || !f.sig.fence_stats ||
+        f.sig.P < 1 || f.sig.P > kMaxFoldInputs || !f.sig.mine || !f.sig.err)
+        return hipErrorInvalidValue;
+    for (int k = 0; k < f.nins; ++k)
+        if (!f.ins[k] || !a.outs[k]) return hipErrorInvalidValue;
+    for (int i = 0; i < f.sig.P; ++i)
+        if (f.sig.pe[i] != f.sig.me && !f.sig.peer[i]) return hipErrorInvalidValue;
+    if (f.lo > f.hi || f.hi > f.n || f.nseg < 0 || f.nseg > kMaxFoldInputs) return hipErrorInvalidValue;
+    for (int k = 0; k < f.nseg; ++k)
+        if (f.glen[k] && (!f.gsrc[k] || !f.gdst[k])) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;   // any pair but the six
+    with_type_op(type, op, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        constexpr int OP = decltype(o)::value;
+        if constexpr (kOwnOrderPair<T, OP>) {
+            hipLaunchKernelGGL((signal_orders2_kernel<T, OP>), dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+            e = hipGetLastError();
+        }
     });
     return e;
 }

@@ -282,6 +282,19 @@ bool fused_oneshot_enabled();
 // ($SHMEMX_FUSED_TWOSHOT_KB, default 4 MiB; 0 turns it off).
 size_t fused_twoshot_bytes();
 long set_fused_twoshot_kb(long kb);   // shmemx_set_fused_twoshot_kb; returns the previous value
+// SIGNAL's own slice ($SHMEMX_SIGNAL_OWNSLICE=1 / shmemx_set_signal_ownslice,
+// default off): the six own-order pairs above the one-shot limit take
+// OWNSLICE's schedule under SIGNAL's device barriers (signal.cpp).  The rule
+// the planner and signal_reduce share: own = own_order_pair on a set of more
+// than one member, bytes = the array's size.
+bool signal_ownslice_enabled();
+long set_signal_ownslice(long on);    // returns the previous value
+inline bool signal_ownslice_route(bool own, size_t bytes) {
+    return own && signal_ownslice_enabled() && bytes > oneshot_bytes();
+}
+// A call ran that schedule (fused: every chunk as one launch): counted in
+// shmemx_direct_stats.
+void count_signal_ownslice_call(bool fused);
 // Hand data between the members' GPUs: fence_and_wait, then the host barrier
 // over the set.
 // Optionally adds the time spent waiting for the stream (from since_us, a
@@ -296,8 +309,10 @@ void node_done(int start, int step, int P, hipStream_t s, double *stream_us = nu
                double *barrier_us = nullptr, double since_us = -1);
 // Map the peers' regions a collective reads (node::peer_base), voting across
 // the set the first time a combination is met; false on every member alike
-// if any member failed (direct.cpp).
-bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set);
+// if any member failed (direct.cpp).  local_ok: something else of this
+// member's that the same vote must carry (its scratch allocation, say).
+bool map_regions(const std::vector<std::pair<node::Region, int>> &regs, const ActiveSet &set,
+                 bool local_ok = true);
 // SIGNAL algorithm (signal.cpp): DIRECT's pulls with device-side barriers,
 // stream-ordered and graph-capturable; symmetric-heap operands only.
 // own_order: every member folds the whole array in its own reference order.

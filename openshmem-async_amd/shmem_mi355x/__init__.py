@@ -127,6 +127,13 @@ def lib() -> ctypes.CDLL:
     L.shmemx_fused_loopback.argtypes = [i, i, i, i, i, i, ctypes.POINTER(vp), ctypes.POINTER(vp), sz,
                                         ctypes.POINTER(ctypes.c_uint), vp]
     L.shmemx_fused_loopback.restype = i
+    L.shmemx_fused_orders_loopback.argtypes = [i, i, i, i, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                               ctypes.POINTER(vp), sz, ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_fused_orders_loopback.restype = i
+    L.shmemx_order_slots_bytes.argtypes = [i, i, sz]
+    L.shmemx_order_slots_bytes.restype = sz
+    L.shmemx_set_signal_ownslice.argtypes = [ctypes.c_long]
+    L.shmemx_set_signal_ownslice.restype = ctypes.c_long
     L.shmemx_reduce_plan.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(Plan)]
     L.shmemx_reduce_plan.restype = i
     L.shmemx_fold_launch_shape.argtypes = [i, i, i, i, sz, ctypes.POINTER(vp), ctypes.POINTER(vp),
@@ -293,6 +300,17 @@ def set_fused_twoshot_kb(kb: int) -> int:
     return prev
 
 
+def set_signal_ownslice(on: bool) -> bool:
+    """shmemx_set_signal_ownslice: SIGNAL takes the six own-order pairs above
+    the one-shot limit through OWNSLICE's schedule under its device barriers
+    (default $SHMEMX_SIGNAL_OWNSLICE, else off); returns the previous setting.
+    Collective in effect: every member must set the same value."""
+    prev = lib().shmemx_set_signal_ownslice(1 if on else 0)
+    if prev < 0:
+        raise ShmemError(1, "shmemx_set_signal_ownslice")
+    return bool(prev)
+
+
 def set_algo(name: str) -> str:
     prev = lib().shmemx_set_algo(ALGOS[name])
     return {v: k for k, v in ALGOS.items()}[prev]
@@ -376,6 +394,33 @@ def fused_loopback(type_name: str, op: str, schedule: int, tgts, srcs, nelems: i
     _check(rc, f"shmemx_fused_loopback({type_name},{op},schedule={schedule},P={P},m={m}): "
                f"error word {err.value}")
     return err.value
+
+
+def fused_orders_loopback(type_name: str, op: str, tgts, srcs, slots, nelems: int, m: int = 0,
+                          stream: int = 0) -> int:
+    """shmemx_fused_orders_loopback: member m's fused own-slice launch
+    (SIGNAL's own slice: the P-order fold of slice m, the mid handshake, the
+    gather of m's slot from every other owner) of a len(tgts)-member set whose
+    sources, targets and slot areas (order_slots_bytes each) are all this
+    process's, with the peer handshakes looped back.  Blocking.  Returns the
+    device barriers' error word (0 when the call returned OK)."""
+    P = len(tgts)
+    if len(srcs) != P or len(slots) != P:
+        raise ValueError("one source and one slot area per target")
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in tgts])
+    b = (ctypes.c_void_p * P)(*[addr(x) for x in srcs])
+    c = (ctypes.c_void_p * P)(*[addr(x) for x in slots])
+    err = ctypes.c_uint(0)
+    rc = lib().shmemx_fused_orders_loopback(TYPES[type_name], OPS[op], P, m, a, b, c, nelems,
+                                            ctypes.byref(err), stream or None)
+    _check(rc, f"shmemx_fused_orders_loopback({type_name},{op},P={P},m={m}): error word {err.value}")
+    return err.value
+
+
+def order_slots_bytes(type_name: str, P: int, nelems: int) -> int:
+    """shmemx_order_slots_bytes: bytes of one member's P - 1 result slots for
+    nelems elements over P members.  Host logic only."""
+    return lib().shmemx_order_slots_bytes(TYPES[type_name], P, nelems)
 
 
 @dataclass
@@ -514,7 +559,14 @@ DIRECT_PHASES = ("entry_wait_us", "entry_barrier_us", "fold_us", "fold_barrier_u
 
 
 FENCE_STATS = ("fences_host", "fence_refills_host", "fences_device", "fences_device_incomplete")
-DIRECT_COUNTS = ("fused_calls", "fused_twoshot_calls", "ownslice_calls")
+# by kind, not by index: the two SIGNAL own-slice counters were appended to
+# shmemx_direct_stats after OWNSLICE's (DIRECT_STAT_INDEX below)
+DIRECT_COUNTS = ("fused_calls", "fused_twoshot_calls", "signal_ownslice_calls",
+                 "signal_ownslice_fused_calls", "ownslice_calls")
+_STATS_IN_ORDER = DIRECT_PHASES + FENCE_STATS + ("fused_calls", "fused_twoshot_calls", "ownslice_calls",
+                                                 "signal_ownslice_calls", "signal_ownslice_fused_calls")
+# name -> index in shmemx_direct_stats' out[]
+DIRECT_STAT_INDEX = {"calls": 0, **{name: k + 1 for k, name in enumerate(_STATS_IN_ORDER)}}
 
 
 def direct_stats(reset: bool = True) -> dict:
@@ -522,14 +574,12 @@ def direct_stats(reset: bool = True) -> dict:
     microseconds summed over them per phase, and the system-fence coverage
     counters (fences checked on the host / refilled because a fence missed an
     XCD; fences checked by the SIGNAL barrier / found incomplete), and the
-    one-shot / two-shot calls that ran as one fused launch and the calls that
-    ran OWNSLICE's two-phase schedule."""
-    names = DIRECT_PHASES + FENCE_STATS + DIRECT_COUNTS
-    buf = (ctypes.c_double * (1 + len(names)))()
+    one-shot / two-shot calls that ran as one fused launch, the calls that
+    ran OWNSLICE's two-phase schedule, and the SIGNAL calls that ran its own
+    slice / ran it with every chunk as one fused launch."""
+    buf = (ctypes.c_double * len(DIRECT_STAT_INDEX))()
     k = lib().shmemx_direct_stats(buf, len(buf), 1 if reset else 0)
-    out = {"calls": buf[0]}
-    out.update({name: buf[i + 1] for i, name in enumerate(names[:max(0, k - 1)])})
-    return out
+    return {name: buf[i] for name, i in DIRECT_STAT_INDEX.items() if i < k}
 
 
 SERVICE_STATS = ("served", "launches", "null_stream_busy", "library_stream_busy", "ns_before_post",

@@ -1,0 +1,23 @@
+"""The chunking of SIGNAL's own slice (set_geom.h order_chunk_elems and the
+slot geometry) as a stand-alone host program under AddressSanitizer and
+UndefinedBehaviorSanitizer (gcc): the chunks tile the array, each chunk's slot
+area fits its half of the scratch, and every member gathers the slot written
+for it (tests/native/test_signal_ownslice_chunks.cpp)."""
+import os
+import subprocess
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "openshmem-async_amd", "csrc")
+SRC = os.path.join(REPO, "tests", "native", "test_signal_ownslice_chunks.cpp")
+
+
+def test_signal_ownslice_chunks_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "signal_ownslice_chunks_san"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I", CSRC, SRC, "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+                                  UBSAN_OPTIONS="print_stacktrace=1"))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.startswith("ok "), out.stdout[-2000:]
+    assert "runtime error" not in out.stderr, out.stderr[-4000:]
