@@ -600,6 +600,100 @@ int shmemx_fused_orders_loopback(int type, int op, int P, int m,
                                  void *const *slots, size_t nelems,
                                  unsigned int *signal_error, void *stream);
 
+/* Stream-ordered barrier, broadcast and fcollect: the collectives of Part 2b
+ * as pure stream work under SIGNAL's device barriers, so a step that holds a
+ * reduction, a broadcast and a barrier can be captured into one hipGraph.  No
+ * host wait, no host barrier and no descriptor exchange: target and source
+ * must both lie in the symmetric heap on every member (every member computes
+ * every peer's address from its own offsets), on a job whose PEs share the
+ * intra-node block.  A call is capturable after one warm call of the same set
+ * has mapped the peers' heaps.  A NULL stream means the runtime's stream.
+ * Calls of one PE, and its SIGNAL reductions, must not overlap in time (one
+ * stream, or stream order between them).  Every member of the set must make
+ * the call with the same sizes, root and settings.
+ *   barrier    the mirrored heap's host stores go to HBM, then a system fence
+ *              on every XCD and the device barrier, on the stream.
+ *   fcollect   member i's nelems elements land at element i * nelems of every
+ *              member's target.  One fused launch while PE_size * nelems *
+ *              size is at most the shmemx_set_fused_twoshot_kb limit, else
+ *              barrier, gather, barrier.  Any overlap of target and source is
+ *              EINVAL.
+ *   broadcast  PE_root is the index in the set, as in the blocking call; the
+ *              root's target is never written.  target == source is allowed,
+ *              a partial overlap is EINVAL.  Up to the
+ *              shmemx_set_bcast_twophase_kb limit, and at PE_size 2, every
+ *              non-root pulls the whole array from the root (one phase).
+ *              Above it the PE_size - 1 non-roots each pull one slice from
+ *              the root and the other slices from each other (two phases: the
+ *              same bytes per GPU over PE_size - 1 links instead of one).
+ *              One fused launch up to the shmemx_set_fused_twoshot_kb limit.
+ * Return SHMEMX_OK or an error code, also left in shmemx_reduce_last_error():
+ * EINVAL, before any HIP call, for a bad set, a root outside 0..PE_size-1, or
+ * NULL operands with nelems > 0; EINVAL for a set that reaches past the job,
+ * ENOTMEMBER for a caller outside the set; ENOTSUP, before any launch, for
+ * operands outside the heap, more than 16 members, or no intra-node block.
+ * nelems == 0 launches nothing, nor does a one-member set (a one-member
+ * fcollect is one stream-ordered copy).
+ * shmem_collect has per-PE counts that only the peers know, which a call
+ * without a descriptor exchange cannot learn: it has no stream-ordered form. */
+int shmemx_barrier_on_stream(int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_broadcast32_on_stream(void *target, const void *source, size_t nelems, int PE_root,
+                                 int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_broadcast64_on_stream(void *target, const void *source, size_t nelems, int PE_root,
+                                 int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_fcollect32_on_stream(void *target, const void *source, size_t nelems,
+                                int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_fcollect64_on_stream(void *target, const void *source, size_t nelems,
+                                int PE_start, int logPE_stride, int PE_size, void *stream);
+
+/* Largest stream-ordered broadcast, in KiB, that stays one phase (default
+ * $SHMEMX_BCAST_TWOPHASE_KB, else 2048: derived, not measured on xGMI; 0 =
+ * two phases whenever PE_size > 2).  Every member of a set must hold the same
+ * value when it calls.  Returns the previous value, or -1 (and EINVAL) for
+ * kb < 0. */
+long shmemx_set_bcast_twophase_kb(long kb);
+
+/* Counts of the stream-ordered calls above since the last reset, up to nout
+ * of them: [0] barriers, [1] broadcasts, [2] fcollects, [3] the calls of [1]
+ * and [2] that ran as one fused launch, [4] two-phase broadcasts (calls that
+ * launched nothing are not counted).  Returns how many were written. */
+int shmemx_pull_stats(unsigned long long *out, int nout, int reset);
+
+/* Pure host logic: how member m's stream-ordered fcollect (kind 0) or
+ * broadcast (kind 1) of nelems elements of esize (4 or 8) bytes over P
+ * members would run under the current limits.  schedule 0: nothing is
+ * launched (no elements, or one member).  nseg_a / nseg_b: the byte ranges m
+ * pulls before / after the mid handshake (the root of a broadcast: none).
+ * lo, hi: the slice m pulls from the root, in elements (two-phase non-root).
+ * EINVAL for kind outside 0..1, esize other than 4 or 8, P outside 1..16, m
+ * outside 0..P-1, for a broadcast a root outside 0..P-1, or a NULL plan. */
+typedef struct { int schedule;   /* 0 none, 1 one-phase, 2 two-phase */
+                 int fused; int nseg_a, nseg_b;
+                 long long lo, hi;            /* my slice, elements (two-phase non-root) */
+               } shmemx_pull_plan_t;
+int shmemx_pull_plan(int kind, size_t esize, size_t nelems, int P, int m, int root,
+                     shmemx_pull_plan_t *plan);
+
+/* Test hook: member m's fused pull launch on one GPU, with no heap and no
+ * peers, the handshakes looped back as shmemx_fused_loopback's (the same 2 s
+ * bound, shared device-side barrier state and device handling); waits for it.
+ *   schedule 0  fcollect: srcs[i]'s nelems elements to element i * nelems of
+ *               tgts[m], for all P members;
+ *   schedule 1  one-phase broadcast: all of srcs[root] to tgts[m];
+ *   schedule 2  two-phase broadcast: m pulls its slice from srcs[root] and
+ *               the other non-roots' slices from whatever the caller put in
+ *               tgts[i].
+ * For m == root a broadcast runs its handshakes and leaves tgts[m] as it was.
+ * tgts[i] may be srcs[i] exactly (broadcast).  *signal_error as for
+ * shmemx_fused_loopback.  Returns OK (at once for nelems == 0); EDEVICE for a
+ * failed launch or a non-zero error word; EINVAL, before any HIP call, for a
+ * schedule outside 0..2, P outside 1..16, m outside 0..P-1, for a broadcast a
+ * root outside 0..P-1, esize other than 4 or 8 or, with nelems > 0, NULL
+ * tgts / srcs or a NULL entry. */
+int shmemx_pull_loopback(int schedule, int P, int m, int root, size_t esize,
+                         void *const *tgts, const void *const *srcs, size_t nelems,
+                         unsigned int *signal_error, void *stream);
+
 /* How a call would be executed (pure host logic, no device needed). */
 typedef struct {
     int algo;          /* resolved SHMEMX_ALGO_* (never AUTO)               */

@@ -201,6 +201,30 @@ struct SignalOrdersArgs {
 };
 hipError_t launch_signal_orders(int type, int op, const SignalOrdersArgs &a, hipStream_t stream);
 
+// The stream-ordered broadcast and fcollect as ONE launch (pull.cpp): the
+// fused two shot above with nothing to fold.  After the entry handshake every
+// block copies its share of list a's byte ranges gsrc[k] -> gdst[k]; with
+// two_phase != 0 (or a non-empty list b) the mid handshake and list b follow;
+// then the exit handshake.  Every member of a set must pass the same
+// two_phase: the handshakes run whatever the lists hold, empty ones too (a
+// broadcast's root).  A list is copied in 16-byte vectors when every
+// segment's source and target are 16-byte aligned, else byte by byte.
+// gsync, sig as for launch_signal_fold.  Its own struct, so the kernarg
+// layout of the launches above does not move.
+struct SegList {
+    int nseg;
+    const void *gsrc[kMaxFoldInputs];
+    void *gdst[kMaxFoldInputs];
+    size_t glen[kMaxFoldInputs];   // bytes
+};
+struct SignalPullArgs {
+    SignalArgs sig;
+    unsigned int *gsync;
+    int two_phase;
+    SegList a, b;
+};
+hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream);
+
 // Position-aware 64-bit checksum of n elements of `type` at device address
 // ptr (16-byte aligned) into out[0], then `epoch` into out[1] (device memory
 // or host-mapped page-locked memory: system-scope stores, in that order),

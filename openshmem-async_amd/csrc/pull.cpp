@@ -1,0 +1,387 @@
+// Stream-ordered barrier, broadcast and fcollect: the
+// collectives next to every reduction, as pure stream work under SIGNAL's
+// device barriers (signal.cpp) — no host wait, no host barrier, no descriptor
+// exchange, capturable into a hipGraph after one warm call of the set has
+// mapped the peers' heaps.
+//
+// Operands must be symmetric — target and source both in the heap on every
+// member — so every member computes every peer's address from its own
+// offsets.  A call whose operands are not returns ENOTSUP before any launch;
+// every refusal depends on what the members share (sizes, offsets, set, root,
+// settings), so no member refuses alone.
+//
+//   barrier    flush of the mirrored heap's view, system fence, signal wave.
+//   fcollect   barrier                 every source is final; nobody reads my target
+//              gather                  all P sources -> my target (set_geom.h
+//                                      fcollect_segments: from member m + 1
+//                                      on, my own copy last)
+//              barrier                 nobody reads my source any more
+//   broadcast  one phase (P == 2, or up to $SHMEMX_BCAST_TWOPHASE_KB): every
+//              non-root pulls the whole array from the root between two
+//              barriers: S over the one link to the root.
+//              two phase (scatter + all-gather): the P - 1 non-roots own the
+//              slices of Slices(nelems, P - 1, esize):
+//              barrier                 the root's source is final
+//              gather A                my slice from the root's source
+//              barrier                 every non-root's slice is final
+//              gather B                the other slices from the other
+//                                      non-roots' targets
+//              barrier                 nobody reads my source or target any more
+//              — 2 S / (P - 1) per link over P - 1 links at once.  The root
+//              runs every barrier and writes nothing (its target is never
+//              written, as in the blocking call).
+// Up to $SHMEMX_FUSED_TWOSHOT_KB (the array for a broadcast, the P-fold target
+// for an fcollect) a call is ONE launch, launch_signal_pull; above it the
+// unfused barriers (launch_sys_fence + launch_signal) around launch_gather.
+//
+// Calls of one PE must not overlap in time (they share the grid barrier's
+// words with SIGNAL's launches): one stream, or stream order between them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "heap.h"
+#include "internal.h"
+#include "node.h"
+#include "set_geom.h"
+#include "shmem_reduce_mi355x.h"
+#include "state.h"
+
+namespace shmx {
+
+namespace {
+
+// The one-phase / two-phase crossover of the broadcast, derived, not measured
+// (unmeasured on xGMI, the first 8-GPU run sets it): one phase
+// costs S / BW, two phases 2 S / ((P - 1) BW) + t for the one handshake more,
+// so S* = t BW (P - 1) / (P - 3); with t = 6.2 us (half of the 12.38 us a
+// whole fused one-shot call with its two handshakes takes,
+// profiles/r05_fused_blocks.txt), BW = 153 GB/s and P = 8: 1.33 MB, rounded
+// up to a power of two in KiB.
+constexpr long kDefaultBcastTwoPhaseKb = 2048;
+
+long twophase_kb_from_env() {
+    const char *e = std::getenv("SHMEMX_BCAST_TWOPHASE_KB");
+    return e ? std::max(0L, std::atol(e)) : kDefaultBcastTwoPhaseKb;
+}
+long g_bcast_twophase_kb = twophase_kb_from_env();
+
+size_t bcast_twophase_bytes() { return size_t(g_bcast_twophase_kb) << 10; }
+
+// shmemx_pull_stats
+enum { kBarriers = 0, kBroadcasts, kFcollects, kFusedCalls, kTwoPhase, kNumStats };
+unsigned long long g_stats[kNumStats];
+
+enum { kFcollect = 0, kBroadcast = 1 };
+
+// How a call of `bytes` per member over P members runs: schedule 0 nothing to
+// do, 1 one phase, 2 two phases; fused: as one launch.  Shared inputs only.
+struct Route {
+    int schedule;
+    bool fused;
+};
+Route route_of(int kind, size_t bytes, int P) {
+    if (!bytes || P < 2) return Route{0, false};
+    if (kind == kFcollect) return Route{1, (size_t)P * bytes <= fused_twoshot_bytes()};
+    const bool two = P > 2 && bytes > bcast_twophase_bytes();
+    return Route{two ? 2 : 1, bytes <= fused_twoshot_bytes()};
+}
+
+bool set_shape_ok(int start, int logstride, int size) {
+    return start >= 0 && logstride >= 0 && logstride <= 30 && size >= 1;
+}
+
+// nelems * esize * 16 members must not wrap
+bool size_ok(size_t esize, size_t nelems) { return nelems <= SIZE_MAX / (esize * kMaxFoldInputs); }
+
+bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+// The caller's set, its index in it and, after map_members, the device
+// barrier's arguments and the members' heap bases.
+struct Members {
+    ActiveSet set;
+    int m = -1;
+    SignalArgs sa;
+    std::vector<char *> hb;
+};
+
+// After the argument checks: the job is up, the set lies inside it and the
+// caller is a member.
+int enter(int start, int logstride, int size, Members *mb) {
+    if (int rc = ensure_init()) return rc;
+    if ((long long)start + (long long)(size - 1) * (1LL << logstride) >= g_state.npes)
+        return set_error(SHMEMX_EINVAL);
+    mb->set = ActiveSet::of(start, logstride, size);
+    if (!is_member(g_state.pe, start, logstride, size, &mb->m)) return set_error(SHMEMX_ENOTMEMBER);
+    return SHMEMX_OK;
+}
+
+// The peers' heap segments (mapped and voted on the first time the set meets
+// them, plain lookups afterwards) and the signal counters in them.
+int map_members(Members *mb) {
+    const int P = mb->set.size;
+    if (!node::up() || P > kMaxFoldInputs || !heap::signal_area()) return set_error(SHMEMX_ENOTSUP);
+    std::vector<std::pair<node::Region, int>> regs;
+    for (int i = 0; i < P; ++i) regs.emplace_back(node::kHeap, mb->set.pe_of(i));
+    if (!map_regions(regs, mb->set)) {
+        trace(LOG_INFO, "stream-ordered pull: a member could not map a peer heap (%s)", node::last_ipc_error());
+        return set_error(SHMEMX_ENOTSUP);
+    }
+    if (!signal_args(mb->set, &mb->sa)) return set_error(SHMEMX_ENOTSUP);
+    mb->hb.resize(P);
+    for (int i = 0; i < P; ++i) mb->hb[i] = node::peer_base(node::kHeap, mb->set.pe_of(i));
+    return SHMEMX_OK;
+}
+
+hipStream_t stream_of(void *stream) {
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : g_state.stream;
+    if (s == g_state.stream) g_state.lib_stream_dirty = true;   // (service.hip)
+    return s;
+}
+
+void device_barrier(const SignalArgs &sa, hipStream_t s) {
+    SHMX_HIP(launch_sys_fence(s, sa.seen));
+    SHMX_HIP(launch_signal(sa, s));
+}
+
+SignalPullArgs pull_args(const SignalArgs &sa, bool two_phase) {
+    SignalPullArgs pa{};
+    pa.sig = sa;
+    pa.gsync = fence_records().gsync;
+    pa.two_phase = two_phase ? 1 : 0;
+    return pa;
+}
+
+// One call's lists, fused or between the unfused barriers.
+void run(const SignalPullArgs &pa, bool fused, hipStream_t s) {
+    if (fused) {
+        SHMX_HIP(launch_signal_pull(pa, s));
+        return;
+    }
+    device_barrier(pa.sig, s);   // every source is final; nobody still reads my target
+    SHMX_HIP(launch_gather(pa.a.gsrc, pa.a.gdst, pa.a.glen, pa.a.nseg, s));
+    if (pa.two_phase) {
+        device_barrier(pa.sig, s);   // every non-root's slice is final
+        SHMX_HIP(launch_gather(pa.b.gsrc, pa.b.gdst, pa.b.glen, pa.b.nseg, s));
+    }
+    device_barrier(pa.sig, s);   // nobody reads my source or target any more
+}
+
+int broadcast_on_stream(size_t esize, void *target, const void *source, size_t nelems, int root, int start,
+                        int logstride, int size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(start, logstride, size) || root < 0 || root >= size || !size_ok(esize, nelems))
+        return set_error(SHMEMX_EINVAL);
+    const size_t bytes = nelems * esize;
+    if (bytes && (!target || !source)) return set_error(SHMEMX_EINVAL);
+    if (bytes && overlap(target, source, bytes)) return set_error(SHMEMX_EINVAL);   // partial; in place is allowed
+    Members mb;
+    if (int rc = enter(start, logstride, size, &mb)) return rc;
+    const int P = size, m = mb.m;
+    trace(LOG_BROADCAST, "stream-ordered: %zu bytes from set member %d, set (%d,%d,%d) member %d", bytes, root,
+          start, logstride, size, m);
+    const Route rt = route_of(kBroadcast, bytes, P);
+    if (!rt.schedule) return SHMEMX_OK;   // the root's target is never written
+    uint64_t soff = 0, toff = 0;
+    if (!heap::offset_of(heap::twin(source), bytes, &soff) || !heap::offset_of(heap::twin(target), bytes, &toff))
+        return set_error(SHMEMX_ENOTSUP);
+    if (int rc = map_members(&mb)) return rc;
+    hipStream_t s = stream_of(stream);
+    // mirrored heap: the root's host stores go to HBM, a non-root's target is
+    // DEVICE_NEWER from here; the root opens no write
+    if (m == root) (void)heap::device_operand(source, bytes);
+    heap::DeviceWrite tw(m == root ? nullptr : target, bytes, s);
+    char *const tgt = mb.hb[m] + toff;
+    const bool two = rt.schedule == 2;
+    const BcastSlices bs(nelems, P, root, esize);
+    SignalPullArgs pa = pull_args(mb.sa, two);
+    pa.a.nseg = bcast_from_root(bs, m, two, mb.hb[root] + soff, tgt, pa.a.gsrc, pa.a.gdst, pa.a.glen);
+    if (two)
+        pa.b.nseg = bcast_from_peers(bs, m, [&](int i) { return mb.hb[i] + toff; }, tgt, pa.b.gsrc, pa.b.gdst,
+                                     pa.b.glen);
+    run(pa, rt.fused, s);
+    g_stats[kBroadcasts] += 1;
+    g_stats[kFusedCalls] += rt.fused;
+    g_stats[kTwoPhase] += two;
+    return SHMEMX_OK;
+}
+
+int fcollect_on_stream(size_t esize, void *target, const void *source, size_t nelems, int start, int logstride,
+                       int size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(start, logstride, size) || !size_ok(esize, nelems)) return set_error(SHMEMX_EINVAL);
+    const size_t nbytes = nelems * esize;
+    if (nbytes && (!target || !source)) return set_error(SHMEMX_EINVAL);
+    if (nbytes && ranges_meet(target, (size_t)size * nbytes, source, nbytes)) return set_error(SHMEMX_EINVAL);
+    Members mb;
+    if (int rc = enter(start, logstride, size, &mb)) return rc;
+    const int P = size, m = mb.m;
+    trace(LOG_COLLECT, "stream-ordered fcollect: %zu bytes mine, set (%d,%d,%d) member %d", nbytes, start, logstride,
+          size, m);
+    if (!nbytes) return SHMEMX_OK;
+    if (P == 1) {
+        // no kernel: the one member's source is its whole result
+        hipStream_t s = stream_of(stream);
+        const void *src = heap::device_operand(source, nbytes);
+        heap::DeviceWrite tw(target, nbytes, s);
+        SHMX_HIP(hipMemcpyAsync(tw.ptr(), src, nbytes, hipMemcpyDefault, s));
+        return SHMEMX_OK;
+    }
+    const Route rt = route_of(kFcollect, nbytes, P);
+    uint64_t soff = 0, toff = 0;
+    if (!heap::offset_of(heap::twin(source), nbytes, &soff) ||
+        !heap::offset_of(heap::twin(target), (size_t)P * nbytes, &toff))
+        return set_error(SHMEMX_ENOTSUP);
+    if (int rc = map_members(&mb)) return rc;
+    hipStream_t s = stream_of(stream);
+    (void)heap::device_operand(source, nbytes);
+    heap::DeviceWrite tw(target, (size_t)P * nbytes, s);
+    SignalPullArgs pa = pull_args(mb.sa, false);
+    pa.a.nseg = fcollect_segments(P, m, nbytes, [&](int i) { return mb.hb[i] + soff; }, mb.hb[m] + toff, pa.a.gsrc,
+                                  pa.a.gdst, pa.a.glen);
+    run(pa, rt.fused, s);
+    g_stats[kFcollects] += 1;
+    g_stats[kFusedCalls] += rt.fused;
+    return SHMEMX_OK;
+}
+
+}  // namespace
+
+}  // namespace shmx
+
+using namespace shmx;
+
+extern "C" {
+
+int shmemx_barrier_on_stream(int PE_start, int logPE_stride, int PE_size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(PE_start, logPE_stride, PE_size)) return set_error(SHMEMX_EINVAL);
+    Members mb;
+    if (int rc = enter(PE_start, logPE_stride, PE_size, &mb)) return rc;
+    trace(LOG_BARRIER, "stream-ordered: set (%d,%d,%d) member %d", PE_start, logPE_stride, PE_size, mb.m);
+    if (PE_size == 1) return SHMEMX_OK;
+    // mirrored heap: the host's stores to symmetric objects reach HBM, where
+    // the peers' kernels read them after the barrier
+    heap::flush_view();
+    if (int rc = map_members(&mb)) return rc;
+    device_barrier(mb.sa, stream_of(stream));
+    g_stats[kBarriers] += 1;
+    return SHMEMX_OK;
+}
+
+int shmemx_broadcast32_on_stream(void *target, const void *source, size_t nelems, int PE_root, int PE_start,
+                                 int logPE_stride, int PE_size, void *stream) {
+    return broadcast_on_stream(4, target, source, nelems, PE_root, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_broadcast64_on_stream(void *target, const void *source, size_t nelems, int PE_root, int PE_start,
+                                 int logPE_stride, int PE_size, void *stream) {
+    return broadcast_on_stream(8, target, source, nelems, PE_root, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_fcollect32_on_stream(void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                                int PE_size, void *stream) {
+    return fcollect_on_stream(4, target, source, nelems, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_fcollect64_on_stream(void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                                int PE_size, void *stream) {
+    return fcollect_on_stream(8, target, source, nelems, PE_start, logPE_stride, PE_size, stream);
+}
+
+long shmemx_set_bcast_twophase_kb(long kb) {
+    if (kb < 0) {
+        set_error(SHMEMX_EINVAL);
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    const long prev = g_bcast_twophase_kb;
+    g_bcast_twophase_kb = kb;
+    return prev;
+}
+
+int shmemx_pull_stats(unsigned long long *out, int nout, int reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    const int k = std::max(0, std::min(nout, (int)kNumStats));
+    for (int i = 0; out && i < k; ++i) out[i] = g_stats[i];
+    if (reset)
+        for (unsigned long long &v : g_stats) v = 0;
+    return out ? k : 0;
+}
+
+int shmemx_pull_plan(int kind, size_t esize, size_t nelems, int P, int m, int root, shmemx_pull_plan_t *plan) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!plan || (kind != kFcollect && kind != kBroadcast) || (esize != 4 && esize != 8) || P < 1 ||
+        P > kMaxFoldInputs || m < 0 || m >= P || (kind == kBroadcast && (root < 0 || root >= P)) ||
+        !size_ok(esize, nelems))
+        return set_error(SHMEMX_EINVAL);
+    *plan = shmemx_pull_plan_t{};
+    const Route rt = route_of(kind, nelems * esize, P);
+    plan->schedule = rt.schedule;
+    if (!rt.schedule) return SHMEMX_OK;
+    plan->fused = rt.fused ? 1 : 0;
+    if (kind == kFcollect) {
+        plan->nseg_a = P;
+        return SHMEMX_OK;
+    }
+    if (m == root) return SHMEMX_OK;   // every handshake, no segment
+    const BcastSlices bs(nelems, P, root, esize);
+    if (rt.schedule == 1) {
+        plan->nseg_a = 1;
+        return SHMEMX_OK;
+    }
+    plan->lo = (long long)bs.lo(m);
+    plan->hi = (long long)bs.hi(m);
+    plan->nseg_a = bs.count(m) ? 1 : 0;
+    for (int i = 0; i < P; ++i) plan->nseg_b += i != m && i != root && bs.count(i) ? 1 : 0;
+    return SHMEMX_OK;
+}
+
+int shmemx_pull_loopback(int schedule, int P, int m, int root, size_t esize, void *const *tgts,
+                         const void *const *srcs, size_t nelems, unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (schedule < 0 || schedule > 2 || P < 1 || P > kMaxFoldInputs || m < 0 || m >= P ||
+        (schedule != 0 && (root < 0 || root >= P)) || (esize != 4 && esize != 8) || !size_ok(esize, nelems))
+        return set_error(SHMEMX_EINVAL);
+    if (nelems == 0) return SHMEMX_OK;
+    if (!tgts || !srcs) return set_error(SHMEMX_EINVAL);
+    for (int i = 0; i < P; ++i)
+        if (!tgts[i] || !srcs[i]) return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalArgs sa{};
+    if (!loopback_signal_args(P, &sa)) return set_error(SHMEMX_ENOMEM);
+    char *const tgt = static_cast<char *>(tgts[m]);
+    SignalPullArgs pa = pull_args(sa, schedule == 2);
+    if (schedule == 0) {
+        pa.a.nseg = fcollect_segments(P, m, nelems * esize, [&](int i) { return static_cast<const char *>(srcs[i]); },
+                                      tgt, pa.a.gsrc, pa.a.gdst, pa.a.glen);
+    } else {
+        const BcastSlices bs(nelems, P, root, esize);
+        pa.a.nseg = bcast_from_root(bs, m, schedule == 2, static_cast<const char *>(srcs[root]), tgt, pa.a.gsrc,
+                                    pa.a.gdst, pa.a.glen);
+        if (schedule == 2)
+            pa.b.nseg = bcast_from_peers(bs, m, [&](int i) { return static_cast<char *>(tgts[i]); }, tgt, pa.b.gsrc,
+                                         pa.b.gdst, pa.b.glen);
+    }
+    hipError_t e = launch_signal_pull(pa, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}
+
+}  // extern "C"

@@ -208,7 +208,7 @@ static const char *const kPlanSettings[] = {
     "SHMEMX_ALLREDUCE_MAX_KB",  "SHMEMX_DIRECT_ONESHOT_KB", "SHMEMX_FUSED_TWOSHOT_KB",
     "SHMEMX_FUSED_ONESHOT",     "SHMEMX_SET_COMMS",         "SHMEMX_SET_COMMS_MAX",
     "SHMEMX_STAGE_CHUNK_MB",    "SHMEMX_DIRECT_SCRATCH_MB", "SHMEMX_TRANSPORT",
-    "SHMEMX_SIGNAL_OWNSLICE"};
+    "SHMEMX_SIGNAL_OWNSLICE",   "SHMEMX_BCAST_TWOPHASE_KB"};
 
 static std::string plan_settings() {
     std::string t;

@@ -114,4 +114,69 @@ inline int gather_order_slots(const Slices &sl, int m, SlotsOf slots_of, char *t
     return k;
 }
 
+// The stream-ordered broadcast (pull.cpp), scatter + all-gather: the P - 1
+// non-roots, in set order, own the slices of Slices(nelems, P - 1, esize);
+// non-root i has slice index (i < root ? i : i - 1) and the root owns nothing.
+// A one-member set has no non-root: its one slice belongs to nobody.
+struct BcastSlices {
+    Slices sl;
+    int P, root;
+    BcastSlices(size_t nelems, int P_, int root_, size_t elem_size)
+        : sl(nelems, P_ > 1 ? P_ - 1 : 1, elem_size), P(P_), root(root_) {}
+    int index(int i) const { return i < root ? i : i - 1; }   // i != root
+    size_t lo(int i) const { return i == root ? 0 : sl.lo(index(i)); }
+    size_t hi(int i) const { return i == root ? 0 : sl.hi(index(i)); }
+    size_t count(int i) const { return hi(i) - lo(i); }
+};
+
+// Phase A of the broadcast: what member m pulls from the root's source at
+// root_src, as byte ranges (room for 1): its slice, to the same place in tgt
+// (two_phase), or the whole array (one phase).  Nothing for the root or an
+// empty range.  Returns how many.
+inline int bcast_from_root(const BcastSlices &b, int m, bool two_phase, const char *root_src, char *tgt,
+                           const void **from, void **to, size_t *len) {
+    if (m == b.root) return 0;
+    const size_t lo = two_phase ? b.lo(m) : 0, hi = two_phase ? b.hi(m) : b.sl.n;
+    if (hi == lo) return 0;
+    from[0] = root_src + lo * b.sl.elem_size;
+    to[0] = tgt + lo * b.sl.elem_size;
+    len[0] = (hi - lo) * b.sl.elem_size;
+    return 1;
+}
+
+// Phase B of the two-phase broadcast: every other non-root's non-empty slice,
+// from that member's target at tgt_of(i), where its phase A put it, to the
+// same place in tgt; from member m + 1 on, wrapping, as the rotated gather
+// above.  Nothing for the root.  Returns how many (room for P - 2).
+template <class TgtOf>
+inline int bcast_from_peers(const BcastSlices &b, int m, TgtOf tgt_of, char *tgt, const void **from, void **to,
+                            size_t *len) {
+    if (m == b.root) return 0;
+    int k = 0;
+    for (int r = 0; r + 1 < b.P; ++r) {
+        const int i = (m + 1 + r) % b.P;
+        if (i == b.root || b.count(i) == 0) continue;
+        const size_t off = b.lo(i) * b.sl.elem_size;
+        from[k] = tgt_of(i) + off;
+        to[k] = tgt + off;
+        len[k++] = b.count(i) * b.sl.elem_size;
+    }
+    return k;
+}
+
+// fcollect: member i's nbytes of source at src_of(i) to tgt + i * nbytes, for
+// all P members, from member m + 1 on, wrapping, m's own copy last.  Returns
+// P (room for P).
+template <class SrcOf>
+inline int fcollect_segments(int P, int m, size_t nbytes, SrcOf src_of, char *tgt, const void **from, void **to,
+                             size_t *len) {
+    for (int r = 0; r < P; ++r) {
+        const int i = (m + 1 + r) % P;
+        from[r] = src_of(i);
+        to[r] = tgt + (size_t)i * nbytes;
+        len[r] = nbytes;
+    }
+    return P;
+}
+
 }  // namespace shmx

@@ -308,14 +308,10 @@ int signal_reduce(int type, int op, char *tgt, const char *src, int nreduce, int
     return SHMEMX_OK;
 }
 
-}  // namespace shmx
-
-using namespace shmx;
-
-// The looped-back handshakes of the test hooks below: PE 0 of PEs 0..P-1 over
-// the private signal area, where peer[i] + me is the word mine + pe[i] the
-// launch has just bumped.  False if the area cannot be had.
-static bool loopback_signal_args(int P, SignalArgs *sa) {
+// The looped-back handshakes of the test hooks below (and pull.cpp's): PE 0 of
+// PEs 0..P-1 over the private signal area, where peer[i] + me is the word
+// mine + pe[i] the launch has just bumped.  False if the area cannot be had.
+bool loopback_signal_args(int P, SignalArgs *sa) {
     *sa = SignalArgs{};
     sa->mine = loopback_signal_area();
     if (!sa->mine) return false;
@@ -335,6 +331,10 @@ static bool loopback_signal_args(int P, SignalArgs *sa) {
     sa->fence_stats = fr.stats;
     return true;
 }
+
+}  // namespace shmx
+
+using namespace shmx;
 
 // Test hook: member m's launch of a P-member set whose members' arrays all
 // belong to this process, with the peer handshakes looped back onto the

@@ -2,7 +2,9 @@
 // (DIRECT, SIGNAL): the system-scope fence on every XCD with
 // its XCD records, the SIGNAL barrier wave, and the fused one-shot and
 // two-shot launches (fence, grid barriers, peer handshakes, fold and gather
-// in one kernel).  The element ops are fold_ops.h's, shared with the fold.
+// in one kernel), and the fused pull of the stream-ordered broadcast and
+// fcollect (the same barriers around one or two gathers).  The element ops
+// are fold_ops.h's, shared with the fold.
 #include "fold_ops.h"
 
 namespace shmx {
@@ -131,7 +133,8 @@ __device__ __forceinline__ T fold_elem(const SignalFoldArgs &a, size_t i) {
 // the last waits for that release; without it such a block returns at once
 // (false), having fenced and arrived, and must leave.  Returns whether this
 // block was the last to arrive; *gen0 is the generation the launch found.
-__device__ __forceinline__ bool fused_entry(const SignalFoldArgs &a, bool wait, unsigned int *gen0_out) {
+template <class Args>   // SignalFoldArgs or SignalPullArgs: their sig and gsync
+__device__ __forceinline__ bool fused_entry(const Args &a, bool wait, unsigned int *gen0_out) {
     unsigned int *const count = a.gsync, *const gen = a.gsync + 1;
     __shared__ int s_last;
     __shared__ unsigned int s_gen0;
@@ -187,7 +190,8 @@ __device__ __forceinline__ bool fused_entry(const SignalFoldArgs &a, bool wait, 
 
 // The exit of a fused launch: the last block to finish reading tells the
 // peers (reduce-op.c:250).
-__device__ __forceinline__ void fused_exit(const SignalFoldArgs &a) {
+template <class Args>
+__device__ __forceinline__ void fused_exit(const Args &a) {
     unsigned int *const count = a.gsync;
     __syncthreads();
     if (threadIdx.x == 0 &&
@@ -305,8 +309,8 @@ __device__ __forceinline__ void fold_span(const SignalFoldArgs &a, size_t tid, s
 // The all-gather of the two-shot: every segment's loads of a step issued
 // before any store, so all peers' links are busy at once (U vectors per
 // segment per lane, as fold_vecs).
-template <int MAXSEG>
-__device__ __forceinline__ void gather_vecs(const SignalFoldArgs &a, size_t nvec, size_t tid, size_t nthr) {
+template <int MAXSEG, class Segs>   // SignalFoldArgs or SegList: their nseg, gsrc, gdst, glen
+__device__ __forceinline__ void gather_vecs(const Segs &a, size_t nvec, size_t tid, size_t nthr) {
     constexpr int U = kMaxFoldInputs / MAXSEG;
     for (size_t v = (tid / kBlock) * kBlock * U + tid % kBlock; v < nvec; v += nthr * U) {
         u32x4 x[MAXSEG][U];
@@ -325,7 +329,8 @@ __device__ __forceinline__ void gather_vecs(const SignalFoldArgs &a, size_t nvec
     }
 }
 
-__device__ __forceinline__ void gather_span(const SignalFoldArgs &a, size_t tid, size_t nthr) {
+template <class Segs>
+__device__ __forceinline__ void gather_span(const Segs &a, size_t tid, size_t nthr) {
     bool vec = true;
     size_t most = 0;
     for (int k = 0; k < a.nseg; ++k) {
@@ -351,7 +356,8 @@ __device__ __forceinline__ void gather_span(const SignalFoldArgs &a, size_t tid,
 // last one does the handshake and releases the generation gen_now + 1; every
 // block then drops stale lines of the peers' memory (system acquire) before
 // it reads what the peers wrote.
-__device__ void grid_handshake(const SignalFoldArgs &a, unsigned int gen_now) {
+template <class Args>
+__device__ void grid_handshake(const Args &a, unsigned int gen_now) {
     unsigned int *const count = a.gsync, *const gen = a.gsync + 1;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -462,6 +468,34 @@ __global__ __launch_bounds__(kBlock) void signal_orders2_kernel(SignalOrdersArgs
     fused_exit(a.f);
 }
 
+// ------------------------------------------------ fused pull (SIGNAL)
+// The stream-ordered broadcast and fcollect (pull.cpp): byte ranges pulled
+// from the peers' heaps under the fused launches' barriers, untyped, one
+// instance.  List a after the entry handshake (fcollect: every member's
+// source; broadcast: this member's part of the root's source); with two_phase
+// a mid handshake (every non-root's slice is final and visible over xGMI) and
+// list b (the other slices from the other non-roots' targets).  Every member
+// of a set runs the same handshakes whatever its lists hold: the root of a
+// broadcast has none and still runs them all.
+//
+// hipcc (ROCm 7), gfx950, -O3: VGPRs / AGPRs / SGPRs / scratch bytes per lane
+// / waves per SIMD
+//     signal_pull_kernel   147 / 0 / 106 / 0 / 3
+// No scratch memory.  Both lists' 3 x 16 words are wave-uniform, more than
+// the SGPR file: 38 SGPRs are parked in VGPR lanes (v_writelane /
+// v_readlane), which the VGPR count includes, as in the own-slice kernel.
+__global__ __launch_bounds__(kBlock) void signal_pull_kernel(SignalPullArgs a) {
+    unsigned int gen0;
+    fused_entry(a, true, &gen0);        // every source is final; nobody still reads my target
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
+    gather_span(a.a, tid, nthr);
+    if (a.two_phase || a.b.nseg > 0) {
+        grid_handshake(a, gen0 + 1u);   // every non-root's slice is final
+        gather_span(a.b, tid, nthr);    // the other slices from the other non-roots' targets
+    }
+    fused_exit(a);                      // nobody reads my source or target any more
+}
+
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
 // check counts them); 8-32 blocks measured within 1 us of it
 // (profiles/r05_fused_blocks.txt).
@@ -521,6 +555,21 @@ hipError_t launch_signal_orders(int type, int op, const SignalOrdersArgs &a, hip
         }
     });
     return e;
+}
+
+hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream) {
+    if (!a.gsync || !a.sig.seen || !a.sig.fence_stats || a.sig.P < 1 || a.sig.P > kMaxFoldInputs || !a.sig.mine ||
+        !a.sig.err)
+        return hipErrorInvalidValue;
+    for (int i = 0; i < a.sig.P; ++i)
+        if (a.sig.pe[i] != a.sig.me && !a.sig.peer[i]) return hipErrorInvalidValue;
+    for (const SegList *l : {&a.a, &a.b}) {
+        if (l->nseg < 0 || l->nseg > kMaxFoldInputs) return hipErrorInvalidValue;
+        for (int k = 0; k < l->nseg; ++k)
+            if (l->glen[k] && (!l->gsrc[k] || !l->gdst[k])) return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(signal_pull_kernel, dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_signal(const SignalArgs &a, hipStream_t stream) {

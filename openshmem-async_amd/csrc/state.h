@@ -252,6 +252,9 @@ FenceRecords fence_records();
 // zeroed counters in device memory, allocated on first use and released with
 // direct_release; nullptr if the allocation failed.
 unsigned long long *loopback_signal_area();
+// SignalArgs of the looped-back test hooks (signal.cpp, pull.cpp): PE 0 of
+// PEs 0..P-1 over that area; false if it cannot be had.
+bool loopback_signal_args(int P, SignalArgs *sa);
 // SignalArgs for the members of a set over their mapped heap segments (the
 // signal counters at heap::signal_offset()); false if this PE has no heap
 // segment or a member's segment is not mapped.

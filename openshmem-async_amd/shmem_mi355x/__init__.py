@@ -51,6 +51,12 @@ class Plan(ctypes.Structure):
                 ("tail", ctypes.c_longlong), ("ws_bytes", ctypes.c_longlong)]
 
 
+class PullPlan(ctypes.Structure):
+    _fields_ = [("schedule", ctypes.c_int), ("fused", ctypes.c_int),
+                ("nseg_a", ctypes.c_int), ("nseg_b", ctypes.c_int),
+                ("lo", ctypes.c_longlong), ("hi", ctypes.c_longlong)]
+
+
 class LaunchShape(ctypes.Structure):
     _fields_ = [("family", ctypes.c_int), ("maxin", ctypes.c_int),
                 ("vectors_per_lane", ctypes.c_int), ("nt", ctypes.c_int),
@@ -132,6 +138,22 @@ def lib() -> ctypes.CDLL:
     L.shmemx_fused_orders_loopback.restype = i
     L.shmemx_order_slots_bytes.argtypes = [i, i, sz]
     L.shmemx_order_slots_bytes.restype = sz
+    L.shmemx_barrier_on_stream.argtypes = [i, i, i, vp]
+    L.shmemx_barrier_on_stream.restype = i
+    for bits in (32, 64):
+        getattr(L, f"shmemx_broadcast{bits}_on_stream").argtypes = [vp, vp, sz, i, i, i, i, vp]
+        getattr(L, f"shmemx_broadcast{bits}_on_stream").restype = i
+        getattr(L, f"shmemx_fcollect{bits}_on_stream").argtypes = [vp, vp, sz, i, i, i, vp]
+        getattr(L, f"shmemx_fcollect{bits}_on_stream").restype = i
+    L.shmemx_set_bcast_twophase_kb.argtypes = [ctypes.c_long]
+    L.shmemx_set_bcast_twophase_kb.restype = ctypes.c_long
+    L.shmemx_pull_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i, i]
+    L.shmemx_pull_stats.restype = i
+    L.shmemx_pull_plan.argtypes = [i, sz, sz, i, i, i, ctypes.POINTER(PullPlan)]
+    L.shmemx_pull_plan.restype = i
+    L.shmemx_pull_loopback.argtypes = [i, i, i, i, sz, ctypes.POINTER(vp), ctypes.POINTER(vp), sz,
+                                       ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_pull_loopback.restype = i
     L.shmemx_set_signal_ownslice.argtypes = [ctypes.c_long]
     L.shmemx_set_signal_ownslice.restype = ctypes.c_long
     L.shmemx_reduce_plan.argtypes = [i, i, i, i, i, i, i, i, i, ctypes.POINTER(Plan)]
@@ -546,6 +568,92 @@ def collect(bits: int, target, source, nelems: int, PE_start: int, logPE_stride:
             PE_size: int, pSync=None) -> None:
     getattr(lib(), f"shmem_collect{bits}")(addr(target), addr(source), nelems, PE_start,
                                            logPE_stride, PE_size, addr(pSync))
+
+
+def barrier_on_stream(PE_start: int, logPE_stride: int, PE_size: int, stream: int = 0) -> None:
+    """shmemx_barrier_on_stream: the set's barrier as stream work (a system
+    fence and the device barrier), capturable."""
+    _check(lib().shmemx_barrier_on_stream(PE_start, logPE_stride, PE_size, stream or None),
+           "shmemx_barrier_on_stream")
+
+
+def broadcast_on_stream(bits: int, target, source, nelems: int, PE_root: int, PE_start: int,
+                        logPE_stride: int, PE_size: int, stream: int = 0) -> None:
+    """shmemx_broadcast{32,64}_on_stream: heap operands only; the root's
+    target is never written."""
+    rc = getattr(lib(), f"shmemx_broadcast{bits}_on_stream")(addr(target), addr(source), nelems, PE_root,
+                                                             PE_start, logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_broadcast{bits}_on_stream")
+
+
+def fcollect_on_stream(bits: int, target, source, nelems: int, PE_start: int, logPE_stride: int,
+                       PE_size: int, stream: int = 0) -> None:
+    """shmemx_fcollect{32,64}_on_stream: heap operands only."""
+    rc = getattr(lib(), f"shmemx_fcollect{bits}_on_stream")(addr(target), addr(source), nelems, PE_start,
+                                                            logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_fcollect{bits}_on_stream")
+
+
+def set_bcast_twophase_kb(kb: int) -> int:
+    """shmemx_set_bcast_twophase_kb: the largest stream-ordered broadcast
+    (KiB) that stays one phase; returns the previous limit.  Collective in
+    effect: every member must set the same value."""
+    prev = lib().shmemx_set_bcast_twophase_kb(kb)
+    if prev < 0:
+        raise ShmemError(1, "shmemx_set_bcast_twophase_kb")
+    return prev
+
+
+PULL_STATS = ("barriers", "broadcasts", "fcollects", "fused_calls", "twophase_broadcasts")
+
+
+def pull_stats(reset: bool = False) -> dict:
+    """shmemx_pull_stats: the stream-ordered barriers, broadcasts and
+    fcollects since the last reset, those of the latter two that ran as one
+    fused launch, and the two-phase broadcasts."""
+    buf = (ctypes.c_ulonglong * len(PULL_STATS))()
+    k = lib().shmemx_pull_stats(buf, len(buf), 1 if reset else 0)
+    return {name: buf[i] for i, name in enumerate(PULL_STATS[:max(0, k)])}
+
+
+PULL_KINDS = {"fcollect": 0, "broadcast": 1}
+
+
+@dataclass
+class PullPlanInfo:
+    schedule: int       # 0 nothing launched, 1 one phase, 2 two phases
+    fused: bool
+    nseg_a: int
+    nseg_b: int
+    lo: int
+    hi: int
+
+
+def pull_plan(kind: str, esize: int, nelems: int, P: int, m: int, root: int = 0) -> PullPlanInfo:
+    """shmemx_pull_plan: how member m's stream-ordered fcollect / broadcast
+    would run under the current limits.  Host logic only."""
+    p = PullPlan()
+    _check(lib().shmemx_pull_plan(PULL_KINDS[kind], esize, nelems, P, m, root, ctypes.byref(p)),
+           f"shmemx_pull_plan({kind},esize={esize},P={P},m={m},root={root})")
+    return PullPlanInfo(p.schedule, bool(p.fused), p.nseg_a, p.nseg_b, p.lo, p.hi)
+
+
+def pull_loopback(schedule: int, tgts, srcs, nelems: int, esize: int, m: int = 0, root: int = 0,
+                  stream: int = 0) -> int:
+    """shmemx_pull_loopback: member m's fused pull launch (schedule 0
+    fcollect, 1 one-phase broadcast, 2 two-phase broadcast) of a
+    len(tgts)-member set whose arrays are all this process's, with the peer
+    handshakes looped back.  Blocking.  Returns the device barriers' error
+    word (0 when the call returned OK)."""
+    P = len(tgts)
+    if len(srcs) != P:
+        raise ValueError("one source per target")
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in tgts])
+    b = (ctypes.c_void_p * P)(*[addr(x) for x in srcs])
+    err = ctypes.c_uint(0)
+    rc = lib().shmemx_pull_loopback(schedule, P, m, root, esize, a, b, nelems, ctypes.byref(err), stream or None)
+    _check(rc, f"shmemx_pull_loopback(schedule={schedule},P={P},m={m},root={root}): error word {err.value}")
+    return err.value
 
 
 def heap_ptr(address: int, pe: int) -> int:

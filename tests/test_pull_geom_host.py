@@ -1,0 +1,24 @@
+"""The geometry of the stream-ordered broadcast and fcollect (set_geom.h) as a
+stand-alone host program under AddressSanitizer and UndefinedBehaviorSanitizer
+(gcc): the non-roots' slices tile the array, every member gathers from a peer
+exactly what that peer pulled from the root, a member's segments never overlap
+and cover its target, and the fcollect segments tile the P-fold target
+(tests/native/test_pull_geom.cpp)."""
+import os
+import subprocess
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "openshmem-async_amd", "csrc")
+SRC = os.path.join(REPO, "tests", "native", "test_pull_geom.cpp")
+
+
+def test_pull_geometry_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "pull_geom_san"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I", CSRC, SRC, "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+                                  UBSAN_OPTIONS="print_stacktrace=1"))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.startswith("ok "), out.stdout[-2000:]
+    assert "runtime error" not in out.stderr, out.stderr[-4000:]
