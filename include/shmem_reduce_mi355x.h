@@ -634,8 +634,9 @@ int shmemx_fused_orders_loopback(int type, int op, int P, int m,
  * operands outside the heap, more than 16 members, or no intra-node block.
  * nelems == 0 launches nothing, nor does a one-member set (a one-member
  * fcollect is one stream-ordered copy).
- * shmem_collect has per-PE counts that only the peers know, which a call
- * without a descriptor exchange cannot learn: it has no stream-ordered form. */
+ * shmem_collect has per-PE counts that only the peers know; its
+ * stream-ordered form, shmemx_collect{32,64}[_counted]_on_stream below,
+ * exchanges them on the device, under the entry barrier. */
 int shmemx_barrier_on_stream(int PE_start, int logPE_stride, int PE_size, void *stream);
 int shmemx_broadcast32_on_stream(void *target, const void *source, size_t nelems, int PE_root,
                                  int PE_start, int logPE_stride, int PE_size, void *stream);
@@ -645,6 +646,88 @@ int shmemx_fcollect32_on_stream(void *target, const void *source, size_t nelems,
                                 int PE_start, int logPE_stride, int PE_size, void *stream);
 int shmemx_fcollect64_on_stream(void *target, const void *source, size_t nelems,
                                 int PE_start, int logPE_stride, int PE_size, void *stream);
+
+/* Stream-ordered collect: shmem_collect{32,64} (member i's nelems_i elements
+ * land at element sum of nelems_j, j < i, of every member's target, in set
+ * order) under the same device barriers and the same rules as the calls above.
+ * No host learns the peers' counts: each member publishes its count in a word
+ * of its heap's signal area before the entry barrier and reads the others'
+ * after it, on the device.
+ *   capacity    the elements the target holds, the same on every member.  It
+ *               is the only size the members share, so the route (one fused
+ *               launch while capacity * size is at most the
+ *               shmemx_set_fused_twoshot_kb limit, else seven launches:
+ *               publish, barrier, plan, copy, barrier) and the grid come from
+ *               it, PE_size and the element size alone.
+ *   _counted    the count is *nelems_dev (8-byte aligned, device-accessible,
+ *               inside the heap or not), read once by the call's first kernel
+ *               when the call EXECUTES: a kernel earlier on the stream may
+ *               have written it, and a graph replay reads it again.
+ *               where_dev, unless NULL, receives two words: this member's
+ *               offset and the total, in elements.
+ * A member-local fact never refuses on the host (a lone refusal would leave
+ * the peers in their barrier's timeout); the device judges it, alike on every
+ * member: a member whose count is above capacity, or whose source would run
+ * past the heap's end or into its target, publishes a poison count (all
+ * ones).  If any count is poison or the total exceeds capacity, every member
+ * writes nothing to its target, stores all ones to both where_dev words,
+ * counts one overflow (shmemx_collect_stats) and still runs the exit
+ * handshake.  The device barriers' error word is not touched: an overflow is
+ * an answer, not a fault, and the next calls are healthy.
+ * EINVAL, before any HIP call: a bad set, capacity * size * 16 wrapping, NULL
+ * or not element-aligned target / source with capacity > 0, a NULL nelems_dev
+ * (counted), nelems_dev / where_dev not 8-byte aligned, a source that STARTS
+ * inside [target, target + capacity * size).  EINVAL / ENOTMEMBER for the set
+ * as above.  ENOTSUP, before any launch: the source's start or the target's
+ * capacity elements outside the heap, more than 16 members, no intra-node
+ * block.  capacity == 0 launches nothing.  A one-member set needs no heap: it
+ * is a copy of the member's own count, through the same kernels. */
+int shmemx_collect32_on_stream(void *target, const void *source, size_t nelems, size_t capacity,
+                               int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_collect64_on_stream(void *target, const void *source, size_t nelems, size_t capacity,
+                               int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_collect32_counted_on_stream(void *target, const void *source,
+                                       const unsigned long long *nelems_dev,
+                                       unsigned long long *where_dev, size_t capacity,
+                                       int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_collect64_counted_on_stream(void *target, const void *source,
+                                       const unsigned long long *nelems_dev,
+                                       unsigned long long *where_dev, size_t capacity,
+                                       int PE_start, int logPE_stride, int PE_size, void *stream);
+
+/* Counts of the stream-ordered collects since the last reset, up to nout of
+ * them: [0] collects, [1] those that ran as one fused launch, [2] overflows
+ * seen on the device (valid once the caller has synchronised the stream; the
+ * loopback hook's launches count here too).  shmemx_pull_stats is unchanged.
+ * Returns how many were written. */
+int shmemx_collect_stats(unsigned long long *out, int nout, int reset);
+
+/* Pure host logic: *fused = 1 if a stream-ordered collect of `capacity`
+ * elements of esize (4 or 8) bytes over P members would run as one fused
+ * launch under the current limit, 0 if unfused or capacity == 0.  EINVAL for
+ * esize other than 4 or 8, P outside 1..16, a wrapping size or a NULL fused. */
+int shmemx_collect_route(size_t esize, size_t capacity, int P, int *fused);
+
+/* Test hook: member m's collect launches on one GPU, set up as
+ * shmemx_pull_loopback (the same 2 s bound, shared device-side barrier state
+ * and device handling, no shmem_init); waits for them.  The count words are a
+ * private 16-word device array: the hook fills the peers' entries from counts
+ * and leaves entry m to the kernel.  With counted != 0, counts[m] is first
+ * copied to a device word the kernel reads.  fused != 0 selects the fused
+ * launch, 0 the seven unfused launches, whatever the capacity.  srcs[m]'s room
+ * ends at tgt where it lies below it.  where_out (unless NULL) receives the
+ * two where words, *overflow_out the overflows this call counted,
+ * *signal_error as for shmemx_fused_loopback.  Returns OK (at once for
+ * capacity == 0); EDEVICE for a failed launch or a non-zero error word;
+ * EINVAL, before any HIP call, for P outside 1..16, m outside 0..P-1, esize
+ * other than 4 or 8, NULL counts, a wrapping capacity or, with capacity > 0,
+ * a NULL or not element-aligned tgt / srcs / entry, or srcs[m] starting
+ * inside the target. */
+int shmemx_collect_loopback(int P, int m, size_t esize, void *tgt, const void *const *srcs,
+                            const unsigned long long *counts, size_t capacity, int fused,
+                            int counted, unsigned long long *where_out,
+                            unsigned int *overflow_out, unsigned int *signal_error,
+                            void *stream);
 
 /* Largest stream-ordered broadcast, in KiB, that stays one phase (default
  * $SHMEMX_BCAST_TWOPHASE_KB, else 2048: derived, not measured on xGMI; 0 =

@@ -28,6 +28,13 @@ constexpr uint64_t kDefaultHeapBytes = uint64_t(4) << 30;
 // counters (signal_area()), zeroed at creation, at the same offset on every
 // PE and mapped by the peers together with the heap.
 constexpr uint64_t kSignalBytes = uint64_t(64) << 10;
+// Past the barrier counters (one 8-byte word per PE of the job, from the
+// area's start): the word in which a member publishes its count for the
+// stream-ordered collect (count_word_offset(), pull.cpp).
+constexpr uint64_t kCountWordOffset = uint64_t(4) << 10;
+static_assert(node::kMaxPes * sizeof(unsigned long long) <= kCountWordOffset &&
+                  kCountWordOffset + sizeof(unsigned long long) <= kSignalBytes,
+              "the count word lies past the counters of the largest job, inside the signal area");
 
 struct Private {
     void *base;     // what hipMalloc returned
@@ -467,6 +474,8 @@ unsigned long long *signal_area() {
 }
 
 uint64_t signal_offset() { return g_heap.arena.capacity(); }
+
+uint64_t count_word_offset() { return kCountWordOffset; }
 
 void *device_operand(const void *p, size_t bytes) {
     if (!in_view(p) || bytes > g_heap.arena.capacity() - (uint64_t)(static_cast<const char *>(p) - g_heap.view))

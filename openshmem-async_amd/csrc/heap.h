@@ -65,6 +65,9 @@ bool is_symmetric(const void *p);
 // PE.  nullptr if there is no segment.
 unsigned long long *signal_area();
 uint64_t signal_offset();
+// The stream-ordered collect's count word (pull.cpp): its byte offset inside
+// the signal area, past the barrier counters of the largest job.
+uint64_t count_word_offset();
 // Mirrored heap (the default, mirror.h).  A collective
 // about to read or write [p, p + bytes): if that range lies in the host view,
 // the host's stores in it go to HBM and the HBM twin's address is returned;

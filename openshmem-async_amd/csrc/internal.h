@@ -225,6 +225,49 @@ struct SignalPullArgs {
 };
 hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream);
 
+// The stream-ordered collect (pull.cpp): the members' counts are exchanged on
+// the device.  Member m publishes its count (`count`, or *count_dev read by
+// the call's first kernel; kCollectPoison if it is above `capacity` or
+// `src_room`, both in elements) in my_word; after the entry barrier one
+// thread reads all P words word[i] (word[m] is my_word), runs collect_plan
+// (set_geom.h) and leaves the plan in `plan` (kCollectPlanWords words of
+// device memory), member m's offset and the total in where[0..2) (all ones
+// on overflow; where may be null) and, on overflow, one more in *overflows
+// (host-mapped; this GPU's launches are its only writer).  Every workgroup
+// then copies its share of the non-empty segments src[i] -> tgt +
+// offset[i] * esize, or nothing on overflow.  esize is 4 or 8 and every
+// pointer a whole number of elements.
+struct CollectArgs {
+    int P, m;
+    unsigned int esize;
+    unsigned long long count;
+    const unsigned long long *count_dev;   // null: `count`
+    unsigned long long capacity, src_room;
+    unsigned long long *my_word;
+    const unsigned long long *word[kMaxFoldInputs];
+    const void *src[kMaxFoldInputs];
+    void *tgt;
+    unsigned long long *plan;
+    unsigned long long *where;
+    unsigned long long *overflows;
+};
+// As ONE launch: publish, the fused launches' entry (the last workgroup's
+// first lane reads the words and plans before it releases the grid), copy,
+// exit.  gsync, sig as for launch_signal_fold.
+struct SignalCollectArgs {
+    SignalArgs sig;
+    unsigned int *gsync;
+    CollectArgs c;
+};
+hipError_t launch_signal_collect(const SignalCollectArgs &a, hipStream_t stream);
+// The same between the unfused barriers: publish (one wave) before the first
+// barrier; plan (one wave) and copy (a sixteenth of the grid copy_blocks
+// gives `capacity` elements, a lane holding 16 units of a step, so every
+// member launches the same shape) after it.
+hipError_t launch_collect_publish(const CollectArgs &c, hipStream_t stream);
+hipError_t launch_collect_plan(const CollectArgs &c, hipStream_t stream);
+hipError_t launch_collect_copy(const CollectArgs &c, hipStream_t stream);
+
 // Position-aware 64-bit checksum of n elements of `type` at device address
 // ptr (16-byte aligned) into out[0], then `epoch` into out[1] (device memory
 // or host-mapped page-locked memory: system-scope stores, in that order),

@@ -30,9 +30,25 @@
 //              — 2 S / (P - 1) per link over P - 1 links at once.  The root
 //              runs every barrier and writes nothing (its target is never
 //              written, as in the blocking call).
+//   collect    the counts are known only to their owners, and no host learns
+//              them: each member publishes its count (an immediate, or a word
+//              of device memory read when the call executes) in a word of its
+//              own signal area, reads the others' after the entry barrier and
+//              derives the layout (set_geom.h collect_plan):
+//              publish                 my count, or poison if it cannot be served
+//              barrier                 every source and count is final
+//              plan                    one thread reads the P counts
+//              copy                    every non-empty source -> its prefix-sum
+//                                      offset of my target (from member m + 1
+//                                      on, my own copy last); nothing on overflow
+//              barrier                 nobody reads my source or count any more
+//              The target's capacity is the one size the members share: the
+//              route and the grid come from it alone.
 // Up to $SHMEMX_FUSED_TWOSHOT_KB (the array for a broadcast, the P-fold target
-// for an fcollect) a call is ONE launch, launch_signal_pull; above it the
-// unfused barriers (launch_sys_fence + launch_signal) around launch_gather.
+// for an fcollect, the target's capacity for a collect) a call is ONE launch,
+// launch_signal_pull / launch_signal_collect; above it the unfused barriers
+// (launch_sys_fence + launch_signal) around launch_gather, or around the
+// collect's publish, plan and copy launches.
 //
 // Calls of one PE must not overlap in time (they share the grid barrier's
 // words with SIGNAL's launches): one stream, or stream order between them.
@@ -253,6 +269,162 @@ int fcollect_on_stream(size_t esize, void *target, const void *source, size_t ne
     return SHMEMX_OK;
 }
 
+// ------------------------------------------------------------- collect
+// shmemx_collect_stats: [collects, those that ran as one fused launch]; the
+// overflows are counted on the device, in CollectState::overflows.
+enum { kCollects = 0, kCollectsFused, kNumCollectStats };
+unsigned long long g_collect_stats[kNumCollectStats];
+
+// What the collect kernels need besides the operands, made on first use
+// (under capture the warm call has made it) and kept: the plan buffer, and a
+// private array of count words, a count and a where[] for the one-member set
+// and the loopback hook, all device memory; the overflow counter, host-mapped.
+struct CollectState {
+    unsigned long long *plan = nullptr;    // kCollectPlanWords
+    unsigned long long *words = nullptr;   // kMaxFoldInputs
+    unsigned long long *count = nullptr;   // 1
+    unsigned long long *where = nullptr;   // 2
+    unsigned long long *overflows = nullptr;
+};
+CollectState g_collect;
+
+bool collect_state() {
+    if (g_collect.plan) return true;
+    void *d = nullptr, *h = nullptr;
+    const size_t words = kCollectPlanWords + kMaxFoldInputs + 1 + 2;
+    if (hipMalloc(&d, words * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(d, 0, words * sizeof(unsigned long long)) != hipSuccess ||
+        hipHostMalloc(&h, sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        return false;
+    }
+    *static_cast<volatile unsigned long long *>(h) = 0;
+    g_collect.plan = static_cast<unsigned long long *>(d);
+    g_collect.words = g_collect.plan + kCollectPlanWords;
+    g_collect.count = g_collect.words + kMaxFoldInputs;
+    g_collect.where = g_collect.count + 1;
+    g_collect.overflows = static_cast<unsigned long long *>(h);
+    return true;
+}
+
+bool collect_route_fused(size_t esize, size_t capacity) { return capacity * esize <= fused_twoshot_bytes(); }
+
+bool elem_aligned(const void *p, size_t esize) { return reinterpret_cast<uintptr_t>(p) % esize == 0; }
+
+// The elements member-local reads of a source at `src` may cover: up to the
+// target where the source lies below it (a source that starts inside the
+// target is refused on the host), and no further than `limit` elements.
+unsigned long long source_room(const char *src, const char *tgt, size_t esize, unsigned long long limit) {
+    if (src < tgt) limit = std::min<unsigned long long>(limit, (unsigned long long)(tgt - src) / esize);
+    return limit;
+}
+
+// One call's launches.  Fused: one.  Unfused: publish, the two launches of a
+// barrier, plan, copy, the two launches of a barrier: seven.
+void run_collect(const SignalCollectArgs &ca, bool fused, hipStream_t s) {
+    if (fused) {
+        SHMX_HIP(launch_signal_collect(ca, s));
+        return;
+    }
+    SHMX_HIP(launch_collect_publish(ca.c, s));
+    device_barrier(ca.sig, s);   // every source and count is final; nobody still reads my target
+    SHMX_HIP(launch_collect_plan(ca.c, s));
+    SHMX_HIP(launch_collect_copy(ca.c, s));
+    device_barrier(ca.sig, s);   // nobody reads my source, my target or my count any more
+}
+
+// The count word.  Each member's count is ONE 8-byte word in its own signal
+// area (heap::count_word_offset(), past the barrier counters); peer i's is at
+// peer_base(i) + signal_offset + that offset, as signal_args finds the
+// counters.  One word per member suffices for every call of every set:
+//   - a peer reads my word only between its entry and its exit handshake of
+//     the call that published it (the exchange follows the entry handshake in
+//     the same thread, or in stream order);
+//   - I overwrite it only in my next call, which starts (stream order, and
+//     calls of one PE never overlap) after my exit handshake of this call has
+//     seen every peer's exit counter, so every peer's read is behind it.
+// A member that is in two sets runs their calls one after the other, so the
+// argument holds across sets too.
+int collect_on_stream(size_t esize, void *target, const void *source, size_t nelems,
+                      const unsigned long long *nelems_dev, unsigned long long *where_dev, bool counted,
+                      size_t capacity, int start, int logstride, int size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(start, logstride, size) || !size_ok(esize, capacity)) return set_error(SHMEMX_EINVAL);
+    if (counted && !nelems_dev) return set_error(SHMEMX_EINVAL);
+    if ((reinterpret_cast<uintptr_t>(nelems_dev) | reinterpret_cast<uintptr_t>(where_dev)) % 8)
+        return set_error(SHMEMX_EINVAL);
+    const size_t cbytes = capacity * esize;
+    if (capacity && (!target || !source)) return set_error(SHMEMX_EINVAL);
+    // whole elements: the offsets are symmetric, so this is a shared fact
+    if (capacity && (!elem_aligned(target, esize) || !elem_aligned(source, esize))) return set_error(SHMEMX_EINVAL);
+    // a source that STARTS inside the target; how far it reaches is a
+    // member-local fact, which the device judges
+    if (capacity && ranges_meet(target, cbytes, source, 1)) return set_error(SHMEMX_EINVAL);
+    Members mb;
+    if (int rc = enter(start, logstride, size, &mb)) return rc;
+    const int P = size, m = mb.m;
+    trace(LOG_COLLECT, "stream-ordered collect: capacity %zu elements of %zu bytes, set (%d,%d,%d) member %d",
+          capacity, esize, start, logstride, size, m);
+    if (!capacity) return SHMEMX_OK;
+    const bool fused = collect_route_fused(esize, capacity);
+    SignalCollectArgs ca{};
+    CollectArgs &c = ca.c;
+    unsigned long long limit = kCollectPoison >> 1;   // the source's room in the heap, elements
+    if (P == 1) {
+        // no peer: any device memory serves, a private count word, no handshake
+        if (!loopback_signal_args(1, &ca.sig) || !collect_state()) return set_error(SHMEMX_ENOMEM);
+        ca.sig.timeout_ticks = signal_timeout_ticks();
+        uint64_t soff = 0;
+        if (heap::offset_of(heap::twin(source), esize, &soff)) limit = (heap::signal_offset() - soff) / esize;
+        c.my_word = g_collect.words;
+        c.word[0] = g_collect.words;
+        c.src[0] = heap::twin(source);
+        c.tgt = heap::twin(target);
+    } else {
+        uint64_t soff = 0, toff = 0;
+        if (!heap::offset_of(heap::twin(source), esize, &soff) || !heap::offset_of(heap::twin(target), cbytes, &toff))
+            return set_error(SHMEMX_ENOTSUP);
+        if (int rc = map_members(&mb)) return rc;
+        if (!collect_state()) return set_error(SHMEMX_ENOMEM);
+        ca.sig = mb.sa;
+        limit = (heap::signal_offset() - soff) / esize;
+        const uint64_t woff = heap::signal_offset() + heap::count_word_offset();
+        for (int i = 0; i < P; ++i) {
+            c.word[i] = reinterpret_cast<const unsigned long long *>(mb.hb[i] + woff);
+            c.src[i] = mb.hb[i] + soff;
+        }
+        c.my_word = reinterpret_cast<unsigned long long *>(mb.hb[m] + woff);
+        c.tgt = mb.hb[m] + toff;
+    }
+    hipStream_t s = stream_of(stream);
+    ca.gsync = fence_records().gsync;
+    c.P = P;
+    c.m = m;
+    c.esize = (unsigned int)esize;
+    c.capacity = capacity;
+    c.src_room = source_room(static_cast<const char *>(c.src[m]), static_cast<const char *>(c.tgt), esize, limit);
+    c.count = counted ? 0 : nelems;
+    c.count_dev = counted ? static_cast<const unsigned long long *>(heap::device_operand(nelems_dev, 8)) : nullptr;
+    c.where = static_cast<unsigned long long *>(heap::twin(where_dev));
+    c.plan = g_collect.plan;
+    c.overflows = g_collect.overflows;
+    // mirrored heap: the host's stores to the source go to HBM for the bound
+    // the host knows (the count, or the room up to the capacity); the target
+    // is DEVICE_NEWER for the whole capacity from here
+    const unsigned long long known = std::min<unsigned long long>(counted ? capacity : std::min(nelems, capacity), limit);
+    (void)heap::device_operand(source, (size_t)known * esize);
+    heap::DeviceWrite tw(target, cbytes, s);
+    heap::DeviceWrite ww(where_dev, where_dev ? 2 * sizeof(unsigned long long) : 0, s);
+    run_collect(ca, fused, s);
+    g_collect_stats[kCollects] += 1;
+    g_collect_stats[kCollectsFused] += fused;
+    return SHMEMX_OK;
+}
+
 }  // namespace
 
 }  // namespace shmx
@@ -296,6 +468,124 @@ int shmemx_fcollect32_on_stream(void *target, const void *source, size_t nelems,
 int shmemx_fcollect64_on_stream(void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
                                 int PE_size, void *stream) {
     return fcollect_on_stream(8, target, source, nelems, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_collect32_on_stream(void *target, const void *source, size_t nelems, size_t capacity, int PE_start,
+                               int logPE_stride, int PE_size, void *stream) {
+    return collect_on_stream(4, target, source, nelems, nullptr, nullptr, false, capacity, PE_start, logPE_stride,
+                             PE_size, stream);
+}
+
+int shmemx_collect64_on_stream(void *target, const void *source, size_t nelems, size_t capacity, int PE_start,
+                               int logPE_stride, int PE_size, void *stream) {
+    return collect_on_stream(8, target, source, nelems, nullptr, nullptr, false, capacity, PE_start, logPE_stride,
+                             PE_size, stream);
+}
+
+int shmemx_collect32_counted_on_stream(void *target, const void *source, const unsigned long long *nelems_dev,
+                                       unsigned long long *where_dev, size_t capacity, int PE_start,
+                                       int logPE_stride, int PE_size, void *stream) {
+    return collect_on_stream(4, target, source, 0, nelems_dev, where_dev, true, capacity, PE_start, logPE_stride,
+                             PE_size, stream);
+}
+
+int shmemx_collect64_counted_on_stream(void *target, const void *source, const unsigned long long *nelems_dev,
+                                       unsigned long long *where_dev, size_t capacity, int PE_start,
+                                       int logPE_stride, int PE_size, void *stream) {
+    return collect_on_stream(8, target, source, 0, nelems_dev, where_dev, true, capacity, PE_start, logPE_stride,
+                             PE_size, stream);
+}
+
+int shmemx_collect_stats(unsigned long long *out, int nout, int reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    volatile unsigned long long *over = g_collect.overflows;   // none before the first launch
+    const unsigned long long all[3] = {g_collect_stats[kCollects], g_collect_stats[kCollectsFused], over ? *over : 0};
+    const int k = std::max(0, std::min(nout, 3));
+    for (int i = 0; out && i < k; ++i) out[i] = all[i];
+    if (reset) {
+        for (unsigned long long &v : g_collect_stats) v = 0;
+        if (over) *over = 0;
+    }
+    return out ? k : 0;
+}
+
+int shmemx_collect_route(size_t esize, size_t capacity, int P, int *fused) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!fused || (esize != 4 && esize != 8) || P < 1 || P > kMaxFoldInputs || !size_ok(esize, capacity))
+        return set_error(SHMEMX_EINVAL);
+    *fused = capacity && collect_route_fused(esize, capacity) ? 1 : 0;
+    return SHMEMX_OK;
+}
+
+int shmemx_collect_loopback(int P, int m, size_t esize, void *tgt, const void *const *srcs,
+                            const unsigned long long *counts, size_t capacity, int fused, int counted,
+                            unsigned long long *where_out, unsigned int *overflow_out,
+                            unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (P < 1 || P > kMaxFoldInputs || m < 0 || m >= P || (esize != 4 && esize != 8) || !size_ok(esize, capacity) ||
+        !counts)
+        return set_error(SHMEMX_EINVAL);
+    if (capacity == 0) return SHMEMX_OK;
+    if (!tgt || !srcs || !elem_aligned(tgt, esize)) return set_error(SHMEMX_EINVAL);
+    for (int i = 0; i < P; ++i)
+        if (!srcs[i] || !elem_aligned(srcs[i], esize)) return set_error(SHMEMX_EINVAL);
+    if (ranges_meet(tgt, capacity * esize, srcs[m], 1)) return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalCollectArgs ca{};
+    if (!loopback_signal_args(P, &ca.sig) || !collect_state()) return set_error(SHMEMX_ENOMEM);
+    ca.gsync = fence_records().gsync;
+    CollectArgs &c = ca.c;
+    c.P = P;
+    c.m = m;
+    c.esize = (unsigned int)esize;
+    c.capacity = capacity;
+    c.src_room = source_room(static_cast<const char *>(srcs[m]), static_cast<const char *>(tgt), esize,
+                             kCollectPoison >> 1);
+    c.count = counted ? 0 : counts[m];
+    c.count_dev = counted ? g_collect.count : nullptr;
+    c.my_word = g_collect.words + m;
+    for (int i = 0; i < P; ++i) {
+        c.word[i] = g_collect.words + i;
+        c.src[i] = srcs[i];
+    }
+    c.tgt = tgt;
+    c.plan = g_collect.plan;
+    c.where = where_out ? g_collect.where : nullptr;
+    c.overflows = g_collect.overflows;
+    // the peers' words as they would have published them; entry m is the
+    // kernel's to write, and holds something no test passes until it has
+    unsigned long long words[kMaxFoldInputs] = {}, stale[2] = {0x5157414c45ull, 0x5157414c45ull};
+    for (int i = 0; i < P; ++i) words[i] = i == m ? 0x5354414c45ull : counts[i];
+    volatile unsigned long long *over = g_collect.overflows;
+    const unsigned long long over0 = *over;
+    hipError_t e = hipMemcpyAsync(g_collect.words, words, sizeof words, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g_collect.count, counts + m, sizeof counts[m], hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g_collect.where, stale, sizeof stale, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) {
+        if (fused) {
+            e = launch_signal_collect(ca, s);
+        } else {
+            e = launch_collect_publish(c, s);
+            if (e == hipSuccess) e = launch_sys_fence(s, ca.sig.seen);
+            if (e == hipSuccess) e = launch_signal(ca.sig, s);
+            if (e == hipSuccess) e = launch_collect_plan(c, s);
+            if (e == hipSuccess) e = launch_collect_copy(c, s);
+            if (e == hipSuccess) e = launch_sys_fence(s, ca.sig.seen);
+            if (e == hipSuccess) e = launch_signal(ca.sig, s);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && where_out) e = hipMemcpy(where_out, g_collect.where, sizeof stale, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (overflow_out) *overflow_out = (unsigned int)(*over - over0);
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
 }
 
 long shmemx_set_bcast_twophase_kb(long kb) {

@@ -2,12 +2,19 @@
 // 16-byte granule, the two-shot slices, the order a member folds its inputs
 // in and the segments it gathers.  Every member of a set must compute these
 // alike (a gather reads a peer's slice where the peer's fold wrote it), so
-// each has one definition here.  Header-only and host-only, so
+// each has one definition here.  Header-only, and host-only but for
+// collect_plan (which the collect kernels run too), so
 // tests/native/test_set_geom.cpp checks it on the CPU.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
+
+#if defined(__HIPCC__)
+#define SHMX_HOST_DEVICE __host__ __device__
+#else
+#define SHMX_HOST_DEVICE
+#endif
 
 namespace shmx {
 
@@ -177,6 +184,53 @@ inline int fcollect_segments(int P, int m, size_t nbytes, SrcOf src_of, char *tg
         len[r] = nbytes;
     }
     return P;
+}
+
+// The stream-ordered collect (pull.cpp): the members learn each other's
+// counts on the device, and every member derives the same layout from them.
+// counts[i] is member i's element count as it published it, or kCollectPoison
+// for a member that could not take part (its count was above the capacity or
+// past its source's room).  Member i's elements land at element offset[i] =
+// sum of counts[j], j < i, of every target; total is the sum.  overflow: a
+// count is poison, or the total is above `capacity` elements or its bytes
+// (times esize) would wrap; the sum saturates at kCollectPoison and never
+// wraps, so every member sees the same overflow.  Nothing may be written
+// then, and nseg is 0.  Otherwise order[0..nseg) are the members whose
+// segments member m copies: from member m + 1 on, wrapping, its own copy
+// last, as fcollect_segments, the empty ones left out.  All words are 8 bytes
+// wide, so the plan travels between workgroups as kCollectPlanWords words.
+constexpr int kCollectMaxMembers = 16;
+constexpr unsigned long long kCollectPoison = ~0ull;
+struct CollectPlan {
+    unsigned long long overflow;   // 0 or 1
+    unsigned long long total;      // elements
+    unsigned long long nseg;
+    unsigned long long offset[kCollectMaxMembers];   // elements
+    unsigned long long count[kCollectMaxMembers];    // the counts as read
+    unsigned long long order[kCollectMaxMembers];    // members
+};
+constexpr int kCollectPlanWords = (int)(sizeof(CollectPlan) / sizeof(unsigned long long));
+
+SHMX_HOST_DEVICE inline void collect_plan(const unsigned long long *counts, int P, unsigned long long capacity,
+                                          unsigned long long esize, int m, CollectPlan *p) {
+    unsigned long long sum = 0;
+    bool bad = false;
+    for (int i = 0; i < P; ++i) {
+        const unsigned long long c = counts[i];
+        p->offset[i] = sum;
+        p->count[i] = c;
+        bad |= c == kCollectPoison;
+        sum = c > kCollectPoison - sum ? kCollectPoison : sum + c;
+    }
+    bad |= sum > capacity || sum > kCollectPoison / esize;
+    p->total = sum;
+    p->overflow = bad ? 1 : 0;
+    int k = 0;
+    for (int r = 0; r < P && !bad; ++r) {
+        const int i = (m + 1 + r) % P;
+        if (counts[i] != 0) p->order[k++] = (unsigned long long)i;
+    }
+    p->nseg = (unsigned long long)k;
 }
 
 }  // namespace shmx

@@ -3,9 +3,12 @@
 // its XCD records, the SIGNAL barrier wave, and the fused one-shot and
 // two-shot launches (fence, grid barriers, peer handshakes, fold and gather
 // in one kernel), and the fused pull of the stream-ordered broadcast and
-// fcollect (the same barriers around one or two gathers).  The element ops
-// are fold_ops.h's, shared with the fold.
+// fcollect (the same barriers around one or two gathers), and the
+// stream-ordered collect (the members' counts exchanged under the entry
+// barrier, fused and unfused).  The element ops are fold_ops.h's, shared with
+// the fold.
 #include "fold_ops.h"
+#include "set_geom.h"   // collect_plan
 
 namespace shmx {
 
@@ -133,8 +136,14 @@ __device__ __forceinline__ T fold_elem(const SignalFoldArgs &a, size_t i) {
 // the last waits for that release; without it such a block returns at once
 // (false), having fenced and arrived, and must leave.  Returns whether this
 // block was the last to arrive; *gen0 is the generation the launch found.
-template <class Args>   // SignalFoldArgs or SignalPullArgs: their sig and gsync
-__device__ __forceinline__ bool fused_entry(const Args &a, bool wait, unsigned int *gen0_out) {
+// hook: what the last block's lane 0 does between the entry handshake and the
+// release of the grid (the collect reads the peers' counts there); nothing
+// unless a launch says so.
+struct NoEntryHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <class Args, class Hook = NoEntryHook>   // Args: their sig and gsync
+__device__ __forceinline__ bool fused_entry(const Args &a, bool wait, unsigned int *gen0_out, Hook hook = Hook()) {
     unsigned int *const count = a.gsync, *const gen = a.gsync + 1;
     __shared__ int s_last;
     __shared__ unsigned int s_gen0;
@@ -180,6 +189,7 @@ __device__ __forceinline__ bool fused_entry(const Args &a, bool wait, unsigned i
         count_coverage(a.sig, rec);
         if (lane == 0) {
             peer_handshake(a.sig);
+            hook();
             __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(gen, s_gen0 + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -496,6 +506,222 @@ __global__ __launch_bounds__(kBlock) void signal_pull_kernel(SignalPullArgs a) {
     fused_exit(a);                      // nobody reads my source or target any more
 }
 
+// ------------------------------------------------ collect (SIGNAL)
+// The stream-ordered collect (pull.cpp): the fused pull with the members'
+// counts exchanged on the device first.  The count word protocol:
+//   publish   one thread stores this member's count (or poison) in its own
+//             word, system scope, BEFORE its block's fence-and-arrive (fused)
+//             or in a kernel before the first barrier's fence (unfused): the
+//             entry handshake's release covers it;
+//   exchange  after the entry handshake ONE thread (the last block's lane 0
+//             before it releases the grid; the plan kernel's lane 0) reads all
+//             P words with system-scope loads, as the counters are polled,
+//             all loads issued before the first is used, runs collect_plan
+//             (set_geom.h) and leaves the plan in a device buffer (8-byte
+//             agent-scope stores), so the blocks do not each read P remote
+//             words; it also stores where[] and counts an overflow;
+//   setup     every block reads the plan (8-byte agent-scope loads, after the
+//             grid's acquire or the kernel boundary) into LDS and lists its
+//             segments there;
+//   copy      collect_span, or nothing on overflow; then the exit handshake.
+// An overflow leaves the SIGNAL error word alone: it is an answer, not a
+// fault, and every member sees the same one.
+//
+// collect_span decides per segment: source and target congruent mod 16 take
+// 16-byte vectors between a head and a tail of element-wide words, any other
+// segment element-wide (4- or 8-byte) words throughout; no byte loop (the
+// operands are whole elements) and no realigned vectors.  As gather_vecs, a
+// lane issues the loads of all segments of a step before any store, U = 16 /
+// MAXSEG units per segment.  The segments are known only on the device, so
+// they live in LDS, not in the kernarg's SGPRs as gather_vecs' do.
+//
+// hipcc (ROCm 7), gfx950, -O3: VGPRs / AGPRs / SGPRs / scratch bytes per lane
+// / LDS bytes / waves per SIMD
+//     signal_collect_kernel    170 / 0 / 106 / 0 / 1328 / 2
+//     collect_copy_kernel      171 / 0 / 106 / 0 / 1200 / 2
+//     collect_publish_kernel     3 / 0 /  18 / 0 /    0 / 8
+//     collect_plan_kernel       33 / 0 /  74 / 0 /  544 / 8
+// No scratch memory.  The copy kernel parks 34 SGPRs in VGPR lanes, which its
+// VGPR count includes; the fused kernel none.  Two waves per SIMD are more
+// than the fused launch's 64 blocks of 4 waves on 256 CUs ever place.
+struct CollectSegs {
+    unsigned long long most;                    // the longest segment's units
+    const char *src[kMaxFoldInputs];            // the body's first byte
+    char *dst[kMaxFoldInputs];
+    unsigned long long units[kMaxFoldInputs];   // 16-byte vectors, or elements
+    unsigned long long len[kMaxFoldInputs];     // bytes, head and tail included
+    unsigned int head[kMaxFoldInputs];          // bytes before the body (vector segments)
+    unsigned int vec[kMaxFoldInputs];
+};
+
+static_assert(kCollectMaxMembers == kMaxFoldInputs, "one member per fold input");
+static_assert(kCollectPlanWords <= 64, "one wave reads the plan");
+
+// one thread
+__device__ __forceinline__ void collect_publish(const CollectArgs &c) {
+    unsigned long long n =
+        c.count_dev ? __hip_atomic_load(c.count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : c.count;
+    if (n > c.capacity || n > c.src_room) n = kCollectPoison;
+    __hip_atomic_store(c.my_word, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// one thread; counts and plan are its block's LDS
+__device__ __forceinline__ void collect_exchange(const CollectArgs &c, unsigned long long *counts,
+                                                 CollectPlan *plan) {
+    unsigned long long x[kMaxFoldInputs];
+#pragma unroll
+    for (int i = 0; i < kMaxFoldInputs; ++i)
+        if (i < c.P) x[i] = __hip_atomic_load(c.word[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+    for (int i = 0; i < kMaxFoldInputs; ++i)
+        if (i < c.P) counts[i] = x[i];
+    collect_plan(counts, c.P, c.capacity, c.esize, c.m, plan);
+    const unsigned long long *w = reinterpret_cast<const unsigned long long *>(plan);
+    for (int k = 0; k < kCollectPlanWords; ++k)
+        __hip_atomic_store(c.plan + k, w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool over = plan->overflow != 0;
+    if (c.where) {
+        __hip_atomic_store(c.where, over ? kCollectPoison : plan->offset[c.m], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(c.where + 1, over ? kCollectPoison : plan->total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (over)   // this GPU's launches, which never overlap, are the only writer
+        __hip_atomic_store(c.overflows,
+                           __hip_atomic_load(c.overflows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + 1,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// every thread of a block: the plan from the device buffer, then the block's
+// segment list (none on overflow)
+__device__ __forceinline__ void collect_setup(const CollectArgs &c, CollectPlan *plan, const void **srcs,
+                                              CollectSegs *g) {
+    unsigned long long *const w = reinterpret_cast<unsigned long long *>(plan);
+    if (threadIdx.x < kCollectPlanWords)
+        w[threadIdx.x] = __hip_atomic_load(c.plan + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kMaxFoldInputs; ++i) srcs[i] = c.src[i];
+    }
+    __syncthreads();
+    const int nseg = plan->nseg <= (unsigned long long)c.P ? (int)plan->nseg : 0;
+    const int k = threadIdx.x;
+    if (k < nseg) {
+        const int i = (int)(plan->order[k] % kMaxFoldInputs);
+        const char *s = static_cast<const char *>(srcs[i]);
+        char *d = static_cast<char *>(c.tgt) + plan->offset[i] * c.esize;
+        const unsigned long long len = plan->count[i] * c.esize;
+        const bool vec = ((reinterpret_cast<uintptr_t>(s) ^ reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+        unsigned long long head = vec ? (16 - (reinterpret_cast<uintptr_t>(s) & 15)) & 15 : 0;
+        if (head > len) head = len;
+        g->src[k] = s + head;
+        g->dst[k] = d + head;
+        g->len[k] = len;
+        g->head[k] = (unsigned int)head;
+        g->vec[k] = vec ? 1u : 0u;
+        g->units[k] = vec ? (len - head) / 16 : len / c.esize;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long most = 0;
+        for (int j = 0; j < nseg; ++j) most = g->units[j] > most ? g->units[j] : most;
+        g->most = most;
+    }
+    __syncthreads();
+}
+
+template <int MAXSEG, typename W>   // W: the element-wide word
+__device__ __forceinline__ void collect_units(const CollectSegs &g, int nseg, size_t tid, size_t nthr) {
+    constexpr int U = kMaxFoldInputs / MAXSEG;
+    const size_t most = g.most;
+    for (size_t v = (tid / kBlock) * kBlock * U + tid % kBlock; v < most; v += nthr * U) {
+        u32x4 x[MAXSEG][U];
+#pragma unroll
+        for (int k = 0; k < MAXSEG; ++k)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k < nseg && v + u * kBlock < g.units[k]) {
+                    if (g.vec[k]) {
+                        x[k][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(g.src[k]) + v + u * kBlock);
+                    } else {
+                        const W e = __builtin_nontemporal_load(reinterpret_cast<const W *>(g.src[k]) + v + u * kBlock);
+                        x[k][u].x = (unsigned int)e;
+                        if constexpr (sizeof(W) == 8) x[k][u].y = (unsigned int)(e >> 32);
+                    }
+                }
+#pragma unroll
+        for (int k = 0; k < MAXSEG; ++k)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k < nseg && v + u * kBlock < g.units[k]) {
+                    if (g.vec[k]) {
+                        reinterpret_cast<u32x4 *>(g.dst[k])[v + u * kBlock] = x[k][u];
+                    } else {
+                        W e = x[k][u].x;
+                        if constexpr (sizeof(W) == 8) e |= (W)x[k][u].y << 32;
+                        reinterpret_cast<W *>(g.dst[k])[v + u * kBlock] = e;
+                    }
+                }
+    }
+}
+
+template <typename W>
+__device__ __forceinline__ void collect_span(const CollectSegs &g, int nseg, size_t tid, size_t nthr) {
+    if (nseg <= 4) collect_units<4, W>(g, nseg, tid, nthr);
+    else if (nseg <= 8) collect_units<8, W>(g, nseg, tid, nthr);
+    else collect_units<16, W>(g, nseg, tid, nthr);
+    // a vector segment's head and tail: fewer than 16 bytes each
+    for (int k = 0; k < nseg; ++k) {
+        if (!g.vec[k]) continue;
+        const size_t head = g.head[k], body = (size_t)g.units[k] * 16;
+        const size_t he = head / sizeof(W), te = ((size_t)g.len[k] - head - body) / sizeof(W);
+        if (tid >= he + te) continue;
+        // relative to the body's first byte
+        const ptrdiff_t off = tid < he ? (ptrdiff_t)(tid * sizeof(W)) - (ptrdiff_t)head
+                                       : (ptrdiff_t)(body + (tid - he) * sizeof(W));
+        *reinterpret_cast<W *>(g.dst[k] + off) = *reinterpret_cast<const W *>(g.src[k] + off);
+    }
+}
+
+__device__ __forceinline__ void collect_copy(const CollectArgs &c, const CollectPlan &plan, const CollectSegs &g) {
+    const int nseg = plan.overflow || plan.nseg > (unsigned long long)c.P ? 0 : (int)plan.nseg;
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
+    if (c.esize == 4) collect_span<unsigned int>(g, nseg, tid, nthr);
+    else collect_span<unsigned long long>(g, nseg, tid, nthr);
+}
+
+__global__ __launch_bounds__(kBlock) void signal_collect_kernel(SignalCollectArgs a) {
+    __shared__ CollectPlan s_plan;
+    __shared__ unsigned long long s_counts[kMaxFoldInputs];
+    __shared__ const void *s_srcs[kMaxFoldInputs];
+    __shared__ CollectSegs s_segs;
+    if (blockIdx.x == 0 && threadIdx.x == 0) collect_publish(a.c);   // before this block's fence-and-arrive
+    unsigned int gen0;
+    // every source and every count is final; nobody still reads my target
+    fused_entry(a, true, &gen0, [&] { collect_exchange(a.c, s_counts, &s_plan); });
+    collect_setup(a.c, &s_plan, s_srcs, &s_segs);
+    collect_copy(a.c, s_plan, s_segs);
+    fused_exit(a);   // nobody reads my source, my target or my count any more
+}
+
+__global__ __launch_bounds__(64) void collect_publish_kernel(CollectArgs c) {
+    if (threadIdx.x == 0) collect_publish(c);
+}
+
+__global__ __launch_bounds__(64) void collect_plan_kernel(CollectArgs c) {
+    __shared__ CollectPlan s_plan;
+    __shared__ unsigned long long s_counts[kMaxFoldInputs];
+    if (threadIdx.x == 0) collect_exchange(c, s_counts, &s_plan);
+}
+
+__global__ __launch_bounds__(kBlock) void collect_copy_kernel(CollectArgs c) {
+    __shared__ CollectPlan s_plan;
+    __shared__ const void *s_srcs[kMaxFoldInputs];
+    __shared__ CollectSegs s_segs;
+    collect_setup(c, &s_plan, s_srcs, &s_segs);
+    collect_copy(c, s_plan, s_segs);
+}
+
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
 // check counts them); 8-32 blocks measured within 1 us of it
 // (profiles/r05_fused_blocks.txt).
@@ -569,6 +795,50 @@ hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream) {
             if (l->glen[k] && (!l->gsrc[k] || !l->gdst[k])) return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(signal_pull_kernel, dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+namespace {
+bool collect_args_ok(const CollectArgs &c) {
+    if (c.P < 1 || c.P > kMaxFoldInputs || c.m < 0 || c.m >= c.P || (c.esize != 4 && c.esize != 8) || !c.my_word ||
+        !c.tgt || !c.plan || !c.overflows || c.capacity > SIZE_MAX / c.esize)
+        return false;
+    if (reinterpret_cast<uintptr_t>(c.tgt) % c.esize ||
+        (reinterpret_cast<uintptr_t>(c.count_dev) | reinterpret_cast<uintptr_t>(c.where)) % 8)
+        return false;
+    for (int i = 0; i < c.P; ++i)
+        if (!c.word[i] || !c.src[i] || reinterpret_cast<uintptr_t>(c.src[i]) % c.esize) return false;
+    return true;
+}
+}  // namespace
+
+hipError_t launch_signal_collect(const SignalCollectArgs &a, hipStream_t stream) {
+    if (!a.gsync || !a.sig.seen || !a.sig.fence_stats || a.sig.P < 1 || a.sig.P > kMaxFoldInputs || !a.sig.mine ||
+        !a.sig.err || !collect_args_ok(a.c))
+        return hipErrorInvalidValue;
+    for (int i = 0; i < a.sig.P; ++i)
+        if (a.sig.pe[i] != a.sig.me && !a.sig.peer[i]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(signal_collect_kernel, dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_collect_publish(const CollectArgs &c, hipStream_t stream) {
+    if (!collect_args_ok(c)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(collect_publish_kernel, dim3(1), dim3(64), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_collect_plan(const CollectArgs &c, hipStream_t stream) {
+    if (!collect_args_ok(c)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(collect_plan_kernel, dim3(1), dim3(64), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_collect_copy(const CollectArgs &c, hipStream_t stream) {
+    if (!collect_args_ok(c)) return hipErrorInvalidValue;
+    // the grid from the capacity alone, which every member shares: a lane holds 16 units of a step
+    const size_t blocks = (copy_blocks(Span16{0, (size_t)(c.capacity * c.esize / 16), 0}) + 15) / kMaxFoldInputs;
+    hipLaunchKernelGGL(collect_copy_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }
 

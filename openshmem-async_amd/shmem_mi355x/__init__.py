@@ -145,6 +145,19 @@ def lib() -> ctypes.CDLL:
         getattr(L, f"shmemx_broadcast{bits}_on_stream").restype = i
         getattr(L, f"shmemx_fcollect{bits}_on_stream").argtypes = [vp, vp, sz, i, i, i, vp]
         getattr(L, f"shmemx_fcollect{bits}_on_stream").restype = i
+    ullp = ctypes.POINTER(ctypes.c_ulonglong)
+    for bits in (32, 64):
+        getattr(L, f"shmemx_collect{bits}_on_stream").argtypes = [vp, vp, sz, sz, i, i, i, vp]
+        getattr(L, f"shmemx_collect{bits}_on_stream").restype = i
+        getattr(L, f"shmemx_collect{bits}_counted_on_stream").argtypes = [vp, vp, vp, vp, sz, i, i, i, vp]
+        getattr(L, f"shmemx_collect{bits}_counted_on_stream").restype = i
+    L.shmemx_collect_stats.argtypes = [ullp, i, i]
+    L.shmemx_collect_stats.restype = i
+    L.shmemx_collect_route.argtypes = [sz, sz, i, ctypes.POINTER(i)]
+    L.shmemx_collect_route.restype = i
+    L.shmemx_collect_loopback.argtypes = [i, i, sz, vp, ctypes.POINTER(vp), ullp, sz, i, i, ullp,
+                                          ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_collect_loopback.restype = i
     L.shmemx_set_bcast_twophase_kb.argtypes = [ctypes.c_long]
     L.shmemx_set_bcast_twophase_kb.restype = ctypes.c_long
     L.shmemx_pull_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i, i]
@@ -614,6 +627,68 @@ def pull_stats(reset: bool = False) -> dict:
     buf = (ctypes.c_ulonglong * len(PULL_STATS))()
     k = lib().shmemx_pull_stats(buf, len(buf), 1 if reset else 0)
     return {name: buf[i] for i, name in enumerate(PULL_STATS[:max(0, k)])}
+
+
+def collect_on_stream(bits: int, target, source, nelems: int, capacity: int, PE_start: int, logPE_stride: int,
+                      PE_size: int, stream: int = 0) -> None:
+    """shmemx_collect{32,64}_on_stream: heap operands only; capacity is the
+    elements the target holds, the same on every member."""
+    rc = getattr(lib(), f"shmemx_collect{bits}_on_stream")(addr(target), addr(source), nelems, capacity, PE_start,
+                                                           logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_collect{bits}_on_stream")
+
+
+def collect_counted_on_stream(bits: int, target, source, nelems_dev, where_dev, capacity: int, PE_start: int,
+                              logPE_stride: int, PE_size: int, stream: int = 0) -> None:
+    """shmemx_collect{32,64}_counted_on_stream: the count is the 8-byte word
+    at nelems_dev when the call executes; where_dev (or None) receives this
+    member's offset and the total."""
+    rc = getattr(lib(), f"shmemx_collect{bits}_counted_on_stream")(
+        addr(target), addr(source), addr(nelems_dev), addr(where_dev), capacity, PE_start, logPE_stride, PE_size,
+        stream or None)
+    _check(rc, f"shmemx_collect{bits}_counted_on_stream")
+
+
+COLLECT_STATS = ("collects", "fused_calls", "overflows")
+ALL_ONES = (1 << 64) - 1
+
+
+def collect_stats(reset: bool = False) -> dict:
+    """shmemx_collect_stats: the stream-ordered collects since the last
+    reset, those that ran as one fused launch, and the overflows the device
+    saw (synchronise the stream first)."""
+    buf = (ctypes.c_ulonglong * len(COLLECT_STATS))()
+    k = lib().shmemx_collect_stats(buf, len(buf), 1 if reset else 0)
+    return {name: buf[i] for i, name in enumerate(COLLECT_STATS[:max(0, k)])}
+
+
+def collect_route(esize: int, capacity: int, P: int) -> bool:
+    """shmemx_collect_route: would a collect of this capacity run as one
+    fused launch under the current limit?  Host logic only."""
+    fused = ctypes.c_int(-1)
+    _check(lib().shmemx_collect_route(esize, capacity, P, ctypes.byref(fused)),
+           f"shmemx_collect_route(esize={esize},capacity={capacity},P={P})")
+    return bool(fused.value)
+
+
+def collect_loopback(tgt, srcs, counts, capacity: int, esize: int, m: int = 0, fused: bool = True,
+                     counted: bool = False, stream: int = 0):
+    """shmemx_collect_loopback: member m's collect launches of a
+    len(srcs)-member set whose arrays are all this process's, the peers'
+    counts given, the handshakes looped back.  Blocking.  Returns (where[0],
+    where[1], overflows counted, the device barriers' error word)."""
+    P = len(srcs)
+    if len(counts) != P:
+        raise ValueError("one count per source")
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in srcs])
+    c = (ctypes.c_ulonglong * P)(*counts)
+    where = (ctypes.c_ulonglong * 2)(0, 0)
+    over, err = ctypes.c_uint(0), ctypes.c_uint(0)
+    rc = lib().shmemx_collect_loopback(P, m, esize, addr(tgt), a, c, capacity, 1 if fused else 0,
+                                       1 if counted else 0, where, ctypes.byref(over), ctypes.byref(err),
+                                       stream or None)
+    _check(rc, f"shmemx_collect_loopback(P={P},m={m},fused={fused},counted={counted}): error word {err.value}")
+    return where[0], where[1], over.value, err.value
 
 
 PULL_KINDS = {"fcollect": 0, "broadcast": 1}
