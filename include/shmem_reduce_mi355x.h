@@ -729,6 +729,105 @@ int shmemx_collect_loopback(int P, int m, size_t esize, void *tgt, const void *c
                             unsigned int *overflow_out, unsigned int *signal_error,
                             void *stream);
 
+/* Stream-ordered alltoall and alltoallv: the personalised exchange (member i
+ * hands a different block to each member j) under the same device barriers
+ * and the same rules as the calls above.
+ * alltoall follows OpenSHMEM 1.3 shmem_alltoall{32,64}: member i's elements
+ * [j * nelems, (j + 1) * nelems) of source land at elements [i * nelems,
+ * (i + 1) * nelems) of member j's target; both arrays hold PE_size * nelems
+ * elements on every member, and any overlap of the two is EINVAL.
+ * alltoallv, per member: send_counts[j] elements starting at element
+ * send_offsets[j] of my source go to member j.  Member m packs what it
+ * receives in set order: sender i's block lands at element sum of
+ * send_counts_k[m], k < i, of m's target (a bucket ordered by sender, as the
+ * collect's).  where_dev, unless NULL, receives PE_size + 1 words: the
+ * element offset of every sender's block, then the total received.
+ *   capacity      the elements the target holds, src_capacity the elements
+ *                 the source holds, both the same on every member.  The route
+ *                 (one fused launch while capacity * size is at most the
+ *                 shmemx_set_fused_twoshot_kb limit, else six launches:
+ *                 barrier, plan, copy, barrier) and the grid come from
+ *                 capacity, PE_size and the element size alone.
+ *   send_counts,  8-byte aligned symmetric-heap arrays of PE_size words, read
+ *   send_offsets  by the PEERS when the call EXECUTES, after the entry
+ *                 handshake: a kernel earlier on any member's stream may have
+ *                 written them, and a graph replay reads them again.  No
+ *                 signal-area word is used.
+ * Target, source and the two tables must be pairwise disjoint.
+ * What a member cannot know the device judges, per receiver: a pair whose
+ * count exceeds src_capacity or whose offset exceeds src_capacity - count (a
+ * peer's garbage never sends a load outside that peer's source), or a total
+ * above capacity.  That member then writes nothing to its target, stores all
+ * ones to all PE_size + 1 where_dev words, counts one overflow
+ * (shmemx_alltoall_stats) and still runs the exit handshake; the other
+ * members complete normally.  The device barriers' error word is not touched.
+ * EINVAL, before any HIP call: a bad set, capacity or src_capacity * size * 16
+ * wrapping (alltoall: PE_size * nelems * size * 16), NULL or not
+ * element-aligned target / source with something to move, NULL tables, tables
+ * or where_dev not 8-byte aligned, any overlap among target, source and the
+ * tables.  EINVAL / ENOTMEMBER for the set as above.  ENOTSUP, before any
+ * launch: target, source or either table outside the heap, more than 16
+ * members, no intra-node block.  capacity == 0 or src_capacity == 0 (alltoall:
+ * nelems == 0) launches nothing and writes no where_dev.  A one-member set
+ * needs no heap and no handshake.
+ * There are NO blocking shmem_alltoall* names: the reference's shmem.h is
+ * OpenSHMEM 1.2 and does not declare them, and its own examples/sample_sort.c
+ * defines shmem_alltoall32 with another signature, so declaring the 1.3
+ * prototype here would break a reference program that builds today.  A
+ * caller who wants the blocking form synchronises the stream. */
+int shmemx_alltoall32_on_stream(void *target, const void *source, size_t nelems,
+                                int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_alltoall64_on_stream(void *target, const void *source, size_t nelems,
+                                int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_alltoallv32_on_stream(void *target, const void *source,
+                                 const unsigned long long *send_counts,
+                                 const unsigned long long *send_offsets,
+                                 unsigned long long *where_dev, size_t capacity, size_t src_capacity,
+                                 int PE_start, int logPE_stride, int PE_size, void *stream);
+int shmemx_alltoallv64_on_stream(void *target, const void *source,
+                                 const unsigned long long *send_counts,
+                                 const unsigned long long *send_offsets,
+                                 unsigned long long *where_dev, size_t capacity, size_t src_capacity,
+                                 int PE_start, int logPE_stride, int PE_size, void *stream);
+
+/* Counts of the stream-ordered alltoalls since the last reset, up to nout of
+ * them: [0] alltoalls, [1] alltoallvs, [2] of those, the ones that ran as one
+ * fused launch, [3] overflows seen on the device (valid once the caller has
+ * synchronised the stream; the loopback hook's launches count here too).
+ * Returns how many were written. */
+int shmemx_alltoall_stats(unsigned long long *out, int nout, int reset);
+
+/* Pure host logic: *fused = 1 if a stream-ordered alltoallv whose target
+ * holds `capacity` elements of esize (4 or 8) bytes (alltoall: PE_size *
+ * nelems) over P members would run as one fused launch under the current
+ * limit, 0 if unfused or capacity == 0.  The limit is the fold's, inherited,
+ * not measured for this call.  EINVAL for esize other than 4 or 8, P outside
+ * 1..16, a wrapping size or a NULL fused. */
+int shmemx_alltoallv_route(size_t esize, size_t capacity, int P, int *fused);
+
+/* Test hook: member m's alltoallv launches on one GPU, set up as
+ * shmemx_collect_loopback (the same 2 s bound, looped-back handshakes, no
+ * shmem_init); waits for them.  counts and offsets are host P x P matrices,
+ * row i what member i sends; the hook copies them to private device tables,
+ * of which member m's kernels read column m.  NULL counts (and offsets) with
+ * capacity = P * nelems runs the fixed alltoall; src_capacity is then taken
+ * as capacity.  fused != 0 selects the fused launch, 0 the six unfused
+ * launches, whatever the capacity.  where_out (unless NULL) receives the
+ * P + 1 where words, *overflow_out the overflows this call counted,
+ * *signal_error as for shmemx_fused_loopback.  Returns OK (at once for
+ * capacity == 0 or src_capacity == 0); EDEVICE for a failed launch or a
+ * non-zero error word; EINVAL, before any HIP call, for P outside 1..16, m
+ * outside 0..P-1, esize other than 4 or 8, a wrapping capacity or
+ * src_capacity, counts without offsets or the reverse, NULL counts with a
+ * capacity that is no multiple of P or, with something to move, a NULL or not
+ * element-aligned tgt / srcs / entry, or a source that meets the target. */
+int shmemx_alltoallv_loopback(int P, int m, size_t esize, void *tgt, const void *const *srcs,
+                              const unsigned long long *counts,
+                              const unsigned long long *offsets, size_t capacity,
+                              size_t src_capacity, int fused, unsigned long long *where_out,
+                              unsigned int *overflow_out, unsigned int *signal_error,
+                              void *stream);
+
 /* Largest stream-ordered broadcast, in KiB, that stays one phase (default
  * $SHMEMX_BCAST_TWOPHASE_KB, else 2048: derived, not measured on xGMI; 0 =
  * two phases whenever PE_size > 2).  Every member of a set must hold the same

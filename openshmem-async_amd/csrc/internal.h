@@ -268,6 +268,46 @@ hipError_t launch_collect_publish(const CollectArgs &c, hipStream_t stream);
 hipError_t launch_collect_plan(const CollectArgs &c, hipStream_t stream);
 hipError_t launch_collect_copy(const CollectArgs &c, hipStream_t stream);
 
+// The stream-ordered alltoall and alltoallv (pull.cpp): the personalised
+// exchange.  Receiver m reads, after the entry barrier, the pair (*cnt[i],
+// *off[i]) from every member i: member i's send_counts[m] and send_offsets[m],
+// words of i's heap; one thread issues all 2 P system-scope loads before it
+// uses the first, runs alltoallv_plan (set_geom.h) and leaves the plan in
+// `plan` (kAlltoallvPlanWords words of device memory), the P block offsets and
+// the total in where[0..P] (all ones on overflow; where may be null) and, on
+// overflow, one more in *overflows (host-mapped; this GPU's launches are its
+// only writer).  Every workgroup then copies its share of the non-empty
+// blocks src[i] + from[i] * esize -> tgt + offset[i] * esize, or nothing on
+// overflow.  cnt[0] == nullptr means immediates and no remote loads (the fixed
+// alltoall): every count `nelems`, every offset m * nelems.  esize is 4 or 8
+// and every pointer a whole number of elements.
+struct AlltoallvArgs {
+    int P, m;
+    unsigned int esize;
+    unsigned long long nelems;   // immediates only
+    unsigned long long capacity, src_capacity;
+    const unsigned long long *cnt[kMaxFoldInputs];
+    const unsigned long long *off[kMaxFoldInputs];
+    const void *src[kMaxFoldInputs];
+    void *tgt;
+    unsigned long long *plan;
+    unsigned long long *where;
+    unsigned long long *overflows;
+};
+// As ONE launch: the fused launches' entry (the last workgroup's first lane
+// reads the pairs and plans before it releases the grid), copy, exit.
+struct SignalAlltoallvArgs {
+    SignalArgs sig;
+    unsigned int *gsync;
+    AlltoallvArgs c;
+};
+hipError_t launch_signal_alltoallv(const SignalAlltoallvArgs &a, hipStream_t stream);
+// The same between the unfused barriers: plan (one wave) and copy (the
+// collect's grid for `capacity` elements, so every member launches the same
+// shape).
+hipError_t launch_alltoallv_plan(const AlltoallvArgs &c, hipStream_t stream);
+hipError_t launch_alltoallv_copy(const AlltoallvArgs &c, hipStream_t stream);
+
 // Position-aware 64-bit checksum of n elements of `type` at device address
 // ptr (16-byte aligned) into out[0], then `epoch` into out[1] (device memory
 // or host-mapped page-locked memory: system-scope stores, in that order),

@@ -44,11 +44,27 @@
 //              barrier                 nobody reads my source or count any more
 //              The target's capacity is the one size the members share: the
 //              route and the grid come from it alone.
+//   alltoallv  the collect's all-to-all generalisation, and the fixed alltoall
+//              with it: member i's send_counts[j] elements from element
+//              send_offsets[j] of its source go to member j, which packs what
+//              it receives in set order.  The two tables are symmetric
+//              objects, final before the entry barrier like the sources, so
+//              nothing is published and no signal-area word is used:
+//              barrier                 every source and table is final
+//              plan                    one thread reads the P (count, offset)
+//                                      pairs meant for me (set_geom.h
+//                                      alltoallv_plan; none for the fixed form)
+//              copy                    every non-empty block -> its prefix-sum
+//                                      offset of my target; nothing if a pair
+//                                      is bad or the total is over capacity
+//              barrier                 nobody reads my source or tables any more
+//              An overflow is the receiver's alone; its peers complete.
 // Up to $SHMEMX_FUSED_TWOSHOT_KB (the array for a broadcast, the P-fold target
-// for an fcollect, the target's capacity for a collect) a call is ONE launch,
-// launch_signal_pull / launch_signal_collect; above it the unfused barriers
-// (launch_sys_fence + launch_signal) around launch_gather, or around the
-// collect's publish, plan and copy launches.
+// for an fcollect, the target's capacity for a collect or an alltoallv) a call
+// is ONE launch, launch_signal_pull / launch_signal_collect /
+// launch_signal_alltoallv; above it the unfused barriers (launch_sys_fence +
+// launch_signal) around launch_gather, or around the collect's publish, plan
+// and copy launches, or the alltoallv's plan and copy.
 //
 // Calls of one PE must not overlap in time (they share the grid barrier's
 // words with SIGNAL's launches): one stream, or stream order between them.
@@ -425,6 +441,156 @@ int collect_on_stream(size_t esize, void *target, const void *source, size_t nel
     return SHMEMX_OK;
 }
 
+// ------------------------------------------------ alltoall, alltoallv
+// shmemx_alltoall_stats: [alltoalls, alltoallvs, of those fused]; the
+// overflows are counted on the device, in AlltoallState::overflows.
+enum { kAlltoalls = 0, kAlltoallvs, kAlltoallFused, kNumAlltoallStats };
+unsigned long long g_alltoall_stats[kNumAlltoallStats];
+
+// What the alltoallv kernels need besides the operands, made on first use
+// (under capture the warm call has made it) and kept: the plan buffer and,
+// for the loopback hook, private P x P count and offset tables and a where[],
+// all device memory; the overflow counter, host-mapped.
+struct AlltoallState {
+    unsigned long long *plan = nullptr;      // kAlltoallvPlanWords
+    unsigned long long *counts = nullptr;    // kMaxFoldInputs^2
+    unsigned long long *offsets = nullptr;   // kMaxFoldInputs^2
+    unsigned long long *where = nullptr;     // kMaxFoldInputs + 1
+    unsigned long long *overflows = nullptr;
+};
+AlltoallState g_alltoall;
+constexpr size_t kTableWords = (size_t)kMaxFoldInputs * kMaxFoldInputs;
+
+bool alltoall_state() {
+    if (g_alltoall.plan) return true;
+    void *d = nullptr, *h = nullptr;
+    const size_t words = kAlltoallvPlanWords + 2 * kTableWords + kMaxFoldInputs + 1;
+    if (hipMalloc(&d, words * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(d, 0, words * sizeof(unsigned long long)) != hipSuccess ||
+        hipHostMalloc(&h, sizeof(unsigned long long), hipHostMallocCoherent) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        return false;
+    }
+    *static_cast<volatile unsigned long long *>(h) = 0;
+    g_alltoall.plan = static_cast<unsigned long long *>(d);
+    g_alltoall.counts = g_alltoall.plan + kAlltoallvPlanWords;
+    g_alltoall.offsets = g_alltoall.counts + kTableWords;
+    g_alltoall.where = g_alltoall.offsets + kTableWords;
+    g_alltoall.overflows = static_cast<unsigned long long *>(h);
+    return true;
+}
+
+// One call's launches.  Fused: one.  Unfused: the two launches of a barrier,
+// plan, copy, the two launches of a barrier: six.  Nothing is published: the
+// tables already live in the heap.
+hipError_t launch_alltoallv(const SignalAlltoallvArgs &aa, bool fused, hipStream_t s) {
+    if (fused) return launch_signal_alltoallv(aa, s);
+    hipError_t e = launch_sys_fence(s, aa.sig.seen);   // every source and table is final; nobody reads my target
+    if (e == hipSuccess) e = launch_signal(aa.sig, s);
+    if (e == hipSuccess) e = launch_alltoallv_plan(aa.c, s);
+    if (e == hipSuccess) e = launch_alltoallv_copy(aa.c, s);
+    if (e == hipSuccess) e = launch_sys_fence(s, aa.sig.seen);   // nobody reads my source or my tables any more
+    if (e == hipSuccess) e = launch_signal(aa.sig, s);
+    return e;
+}
+
+// counts == nullptr: the fixed alltoall of `nelems` elements per pair
+// (capacity == src_capacity == size * nelems, the caller's product).
+int alltoallv_on_stream(size_t esize, void *target, const void *source, const unsigned long long *counts,
+                        const unsigned long long *offsets, bool fixed, size_t nelems, unsigned long long *where_dev,
+                        size_t capacity, size_t src_capacity, int start, int logstride, int size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(start, logstride, size)) return set_error(SHMEMX_EINVAL);
+    if (fixed) {
+        if (nelems > SIZE_MAX / (esize * kMaxFoldInputs) / (size_t)size) return set_error(SHMEMX_EINVAL);
+        capacity = src_capacity = (size_t)size * nelems;
+    }
+    if (!size_ok(esize, capacity) || !size_ok(esize, src_capacity)) return set_error(SHMEMX_EINVAL);
+    const size_t cbytes = capacity * esize, sbytes = src_capacity * esize;
+    const size_t tbytes = (size_t)size * sizeof(unsigned long long);
+    const bool work = capacity && src_capacity;
+    if (!fixed && (!counts || !offsets)) return set_error(SHMEMX_EINVAL);
+    if ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(offsets) |
+         reinterpret_cast<uintptr_t>(where_dev)) % 8)
+        return set_error(SHMEMX_EINVAL);
+    if (work && (!target || !source)) return set_error(SHMEMX_EINVAL);
+    // whole elements: the offsets are symmetric, so this is a shared fact
+    if (work && (!elem_aligned(target, esize) || !elem_aligned(source, esize))) return set_error(SHMEMX_EINVAL);
+    // target, source and the two tables pairwise disjoint: symmetric offsets again
+    if (work && ranges_meet(target, cbytes, source, sbytes)) return set_error(SHMEMX_EINVAL);
+    if (work && !fixed &&
+        (ranges_meet(target, cbytes, counts, tbytes) || ranges_meet(target, cbytes, offsets, tbytes) ||
+         ranges_meet(source, sbytes, counts, tbytes) || ranges_meet(source, sbytes, offsets, tbytes) ||
+         ranges_meet(counts, tbytes, offsets, tbytes)))
+        return set_error(SHMEMX_EINVAL);
+    Members mb;
+    if (int rc = enter(start, logstride, size, &mb)) return rc;
+    const int P = size, m = mb.m;
+    trace(LOG_COLLECT, "stream-ordered alltoall%s: capacity %zu, source %zu elements of %zu bytes, set (%d,%d,%d) member %d",
+          fixed ? "" : "v", capacity, src_capacity, esize, start, logstride, size, m);
+    if (!work) return SHMEMX_OK;
+    const bool fused = collect_route_fused(esize, capacity);
+    SignalAlltoallvArgs aa{};
+    AlltoallvArgs &c = aa.c;
+    if (P == 1) {
+        // no peer: any device memory serves, no handshake
+        if (!loopback_signal_args(1, &aa.sig) || !alltoall_state()) return set_error(SHMEMX_ENOMEM);
+        aa.sig.timeout_ticks = signal_timeout_ticks();
+        c.src[0] = heap::twin(source);
+        c.tgt = heap::twin(target);
+        if (!fixed) {
+            c.cnt[0] = static_cast<const unsigned long long *>(heap::twin(counts));
+            c.off[0] = static_cast<const unsigned long long *>(heap::twin(offsets));
+        }
+    } else {
+        uint64_t soff = 0, toff = 0, coff = 0, ooff = 0;
+        if (!heap::offset_of(heap::twin(source), sbytes, &soff) || !heap::offset_of(heap::twin(target), cbytes, &toff))
+            return set_error(SHMEMX_ENOTSUP);
+        if (!fixed && (!heap::offset_of(heap::twin(counts), tbytes, &coff) ||
+                       !heap::offset_of(heap::twin(offsets), tbytes, &ooff)))
+            return set_error(SHMEMX_ENOTSUP);
+        if (int rc = map_members(&mb)) return rc;
+        if (!alltoall_state()) return set_error(SHMEMX_ENOMEM);
+        aa.sig = mb.sa;
+        for (int i = 0; i < P; ++i) {
+            c.src[i] = mb.hb[i] + soff;
+            if (fixed) continue;
+            // member i's pair for me: word m of its tables
+            c.cnt[i] = reinterpret_cast<const unsigned long long *>(mb.hb[i] + coff) + m;
+            c.off[i] = reinterpret_cast<const unsigned long long *>(mb.hb[i] + ooff) + m;
+        }
+        c.tgt = mb.hb[m] + toff;
+    }
+    hipStream_t s = stream_of(stream);
+    aa.gsync = fence_records().gsync;
+    c.P = P;
+    c.m = m;
+    c.esize = (unsigned int)esize;
+    c.nelems = fixed ? nelems : 0;
+    c.capacity = capacity;
+    c.src_capacity = src_capacity;
+    c.where = static_cast<unsigned long long *>(heap::twin(where_dev));
+    c.plan = g_alltoall.plan;
+    c.overflows = g_alltoall.overflows;
+    // mirrored heap: the host's stores to the source and the tables go to HBM;
+    // the target's capacity and where_dev are DEVICE_NEWER from here
+    (void)heap::device_operand(source, sbytes);
+    if (!fixed) {
+        (void)heap::device_operand(counts, tbytes);
+        (void)heap::device_operand(offsets, tbytes);
+    }
+    heap::DeviceWrite tw(target, cbytes, s);
+    heap::DeviceWrite ww(where_dev, where_dev ? (size_t)(P + 1) * sizeof(unsigned long long) : 0, s);
+    SHMX_HIP(launch_alltoallv(aa, fused, s));
+    g_alltoall_stats[fixed ? kAlltoalls : kAlltoallvs] += 1;
+    g_alltoall_stats[kAlltoallFused] += fused;
+    return SHMEMX_OK;
+}
+
 }  // namespace
 
 }  // namespace shmx
@@ -580,6 +746,122 @@ int shmemx_collect_loopback(int P, int m, size_t esize, void *tgt, const void *c
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess && where_out) e = hipMemcpy(where_out, g_collect.where, sizeof stale, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (overflow_out) *overflow_out = (unsigned int)(*over - over0);
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}
+
+int shmemx_alltoall32_on_stream(void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                                int PE_size, void *stream) {
+    return alltoallv_on_stream(4, target, source, nullptr, nullptr, true, nelems, nullptr, 0, 0, PE_start,
+                               logPE_stride, PE_size, stream);
+}
+
+int shmemx_alltoall64_on_stream(void *target, const void *source, size_t nelems, int PE_start, int logPE_stride,
+                                int PE_size, void *stream) {
+    return alltoallv_on_stream(8, target, source, nullptr, nullptr, true, nelems, nullptr, 0, 0, PE_start,
+                               logPE_stride, PE_size, stream);
+}
+
+int shmemx_alltoallv32_on_stream(void *target, const void *source, const unsigned long long *send_counts,
+                                 const unsigned long long *send_offsets, unsigned long long *where_dev,
+                                 size_t capacity, size_t src_capacity, int PE_start, int logPE_stride, int PE_size,
+                                 void *stream) {
+    return alltoallv_on_stream(4, target, source, send_counts, send_offsets, false, 0, where_dev, capacity,
+                               src_capacity, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_alltoallv64_on_stream(void *target, const void *source, const unsigned long long *send_counts,
+                                 const unsigned long long *send_offsets, unsigned long long *where_dev,
+                                 size_t capacity, size_t src_capacity, int PE_start, int logPE_stride, int PE_size,
+                                 void *stream) {
+    return alltoallv_on_stream(8, target, source, send_counts, send_offsets, false, 0, where_dev, capacity,
+                               src_capacity, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_alltoall_stats(unsigned long long *out, int nout, int reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    volatile unsigned long long *over = g_alltoall.overflows;   // none before the first launch
+    const unsigned long long all[4] = {g_alltoall_stats[kAlltoalls], g_alltoall_stats[kAlltoallvs],
+                                       g_alltoall_stats[kAlltoallFused], over ? *over : 0};
+    const int k = std::max(0, std::min(nout, 4));
+    for (int i = 0; out && i < k; ++i) out[i] = all[i];
+    if (reset) {
+        for (unsigned long long &v : g_alltoall_stats) v = 0;
+        if (over) *over = 0;
+    }
+    return out ? k : 0;
+}
+
+int shmemx_alltoallv_route(size_t esize, size_t capacity, int P, int *fused) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!fused || (esize != 4 && esize != 8) || P < 1 || P > kMaxFoldInputs || !size_ok(esize, capacity))
+        return set_error(SHMEMX_EINVAL);
+    *fused = capacity && collect_route_fused(esize, capacity) ? 1 : 0;
+    return SHMEMX_OK;
+}
+
+int shmemx_alltoallv_loopback(int P, int m, size_t esize, void *tgt, const void *const *srcs,
+                              const unsigned long long *counts, const unsigned long long *offsets, size_t capacity,
+                              size_t src_capacity, int fused, unsigned long long *where_out,
+                              unsigned int *overflow_out, unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (P < 1 || P > kMaxFoldInputs || m < 0 || m >= P || (esize != 4 && esize != 8) || !size_ok(esize, capacity))
+        return set_error(SHMEMX_EINVAL);
+    const bool fixed = !counts;
+    if (fixed) {
+        if (offsets || capacity % (size_t)P) return set_error(SHMEMX_EINVAL);
+        src_capacity = capacity;
+    } else if (!offsets || !size_ok(esize, src_capacity)) {
+        return set_error(SHMEMX_EINVAL);
+    }
+    if (capacity == 0 || src_capacity == 0) return SHMEMX_OK;
+    if (!tgt || !srcs || !elem_aligned(tgt, esize)) return set_error(SHMEMX_EINVAL);
+    for (int i = 0; i < P; ++i)
+        if (!srcs[i] || !elem_aligned(srcs[i], esize) ||
+            ranges_meet(tgt, capacity * esize, srcs[i], src_capacity * esize))
+            return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalAlltoallvArgs aa{};
+    if (!loopback_signal_args(P, &aa.sig) || !alltoall_state()) return set_error(SHMEMX_ENOMEM);
+    aa.gsync = fence_records().gsync;
+    AlltoallvArgs &c = aa.c;
+    c.P = P;
+    c.m = m;
+    c.esize = (unsigned int)esize;
+    c.nelems = fixed ? capacity / (size_t)P : 0;
+    c.capacity = capacity;
+    c.src_capacity = src_capacity;
+    for (int i = 0; i < P; ++i) {
+        c.src[i] = srcs[i];
+        if (fixed) continue;
+        c.cnt[i] = g_alltoall.counts + (size_t)i * P + m;   // row i is what member i sends
+        c.off[i] = g_alltoall.offsets + (size_t)i * P + m;
+    }
+    c.tgt = tgt;
+    c.plan = g_alltoall.plan;
+    c.where = where_out ? g_alltoall.where : nullptr;
+    c.overflows = g_alltoall.overflows;
+    // where[] holds something no test passes until the kernel has written it
+    unsigned long long stale[kMaxFoldInputs + 1];
+    for (unsigned long long &v : stale) v = 0x5157414c45ull;
+    const size_t wbytes = (size_t)(P + 1) * sizeof(unsigned long long);
+    const size_t tbytes = (size_t)P * P * sizeof(unsigned long long);
+    volatile unsigned long long *over = g_alltoall.overflows;
+    const unsigned long long over0 = *over;
+    hipError_t e = hipMemcpyAsync(g_alltoall.where, stale, wbytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !fixed) e = hipMemcpyAsync(g_alltoall.counts, counts, tbytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !fixed) e = hipMemcpyAsync(g_alltoall.offsets, offsets, tbytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = launch_alltoallv(aa, fused != 0, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && where_out) e = hipMemcpy(where_out, g_alltoall.where, wbytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) (void)hipGetLastError();
     const unsigned int err = signal_error();
     if (signal_error_out) *signal_error_out = err;

@@ -3,7 +3,7 @@
 // in and the segments it gathers.  Every member of a set must compute these
 // alike (a gather reads a peer's slice where the peer's fold wrote it), so
 // each has one definition here.  Header-only, and host-only but for
-// collect_plan (which the collect kernels run too), so
+// collect_plan and alltoallv_plan (which the kernels run too), so
 // tests/native/test_set_geom.cpp checks it on the CPU.
 #pragma once
 
@@ -220,6 +220,55 @@ SHMX_HOST_DEVICE inline void collect_plan(const unsigned long long *counts, int 
         p->offset[i] = sum;
         p->count[i] = c;
         bad |= c == kCollectPoison;
+        sum = c > kCollectPoison - sum ? kCollectPoison : sum + c;
+    }
+    bad |= sum > capacity || sum > kCollectPoison / esize;
+    p->total = sum;
+    p->overflow = bad ? 1 : 0;
+    int k = 0;
+    for (int r = 0; r < P && !bad; ++r) {
+        const int i = (m + 1 + r) % P;
+        if (counts[i] != 0) p->order[k++] = (unsigned long long)i;
+    }
+    p->nseg = (unsigned long long)k;
+}
+
+// The stream-ordered alltoallv (pull.cpp): receiver m reads, from each member
+// i, the pair (send_counts_i[m], send_offsets_i[m]) and packs what it receives
+// in set order.  counts[i] / offsets[i] are those pairs as read; sender i's
+// block of counts[i] elements, which starts at element from[i] = offsets[i] of
+// i's source, lands at element offset[i] = sum of counts[k], k < i, of m's
+// target; total is the sum.  A pair is bad if its count is above
+// `src_capacity` (the elements every source holds) or its offset above
+// src_capacity - count: a peer's garbage must never send a load outside that
+// peer's source.  overflow: a bad pair, or the total above `capacity` or its
+// bytes (times esize) wrapping; the sum saturates at kCollectPoison.  Nothing
+// may be written then, and nseg is 0.  Otherwise order[0..nseg) as in
+// collect_plan: from member m + 1 on, wrapping, m's own block last, the empty
+// ones left out.  The fixed alltoall is the same plan with immediates: every
+// count nelems, every offset m * nelems, both capacities P * nelems.
+struct AlltoallvPlan {
+    unsigned long long overflow;   // 0 or 1
+    unsigned long long total;      // elements
+    unsigned long long nseg;
+    unsigned long long offset[kCollectMaxMembers];   // elements, in m's target
+    unsigned long long count[kCollectMaxMembers];    // the counts as read
+    unsigned long long order[kCollectMaxMembers];    // members
+    unsigned long long from[kCollectMaxMembers];     // elements, in sender i's source
+};
+constexpr int kAlltoallvPlanWords = (int)(sizeof(AlltoallvPlan) / sizeof(unsigned long long));
+
+SHMX_HOST_DEVICE inline void alltoallv_plan(const unsigned long long *counts, const unsigned long long *offsets, int P,
+                                            unsigned long long capacity, unsigned long long src_capacity,
+                                            unsigned long long esize, int m, AlltoallvPlan *p) {
+    unsigned long long sum = 0;
+    bool bad = false;
+    for (int i = 0; i < P; ++i) {
+        const unsigned long long c = counts[i], o = offsets[i];
+        p->offset[i] = sum;
+        p->count[i] = c;
+        p->from[i] = o;
+        bad |= c > src_capacity || o > src_capacity - c;
         sum = c > kCollectPoison - sum ? kCollectPoison : sum + c;
     }
     bad |= sum > capacity || sum > kCollectPoison / esize;

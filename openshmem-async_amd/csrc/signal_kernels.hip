@@ -5,10 +5,11 @@
 // in one kernel), and the fused pull of the stream-ordered broadcast and
 // fcollect (the same barriers around one or two gathers), and the
 // stream-ordered collect (the members' counts exchanged under the entry
-// barrier, fused and unfused).  The element ops are fold_ops.h's, shared with
-// the fold.
+// barrier, fused and unfused), and the stream-ordered alltoall and alltoallv
+// (the peers' count and offset tables read under the entry barrier).  The
+// element ops are fold_ops.h's, shared with the fold.
 #include "fold_ops.h"
-#include "set_geom.h"   // collect_plan
+#include "set_geom.h"   // collect_plan, alltoallv_plan
 
 namespace shmx {
 
@@ -722,6 +723,151 @@ __global__ __launch_bounds__(kBlock) void collect_copy_kernel(CollectArgs c) {
     collect_copy(c, s_plan, s_segs);
 }
 
+// ------------------------------------------------ alltoallv (SIGNAL)
+// The stream-ordered alltoall and alltoallv (pull.cpp): the collect's
+// all-to-all generalisation.  Nothing is published: the count and offset
+// tables are ordinary symmetric objects, final before their owner's entry
+// handshake like every source.
+//   exchange  after the entry handshake ONE thread (the last block's lane 0
+//             before it releases the grid; the plan kernel's lane 0) reads the
+//             pair (send_counts_i[m], send_offsets_i[m]) of every member i
+//             with system-scope loads, all 2 P issued before the first is
+//             used, runs alltoallv_plan (set_geom.h), which rejects a pair
+//             that would read outside its sender's source, and leaves the
+//             plan in a device buffer (8-byte agent-scope stores); it also
+//             stores where[0..P] and counts an overflow.  With immediates
+//             (the fixed alltoall: cnt[0] is null) it loads nothing;
+//   setup     every block reads the plan (8-byte agent-scope loads) into LDS
+//             and lists its segments there, sender i's from
+//             src[i] + from[i] * esize;
+//   copy      collect_span, under its rule, or nothing on overflow; then the
+//             exit handshake.
+// The overflow is this receiver's alone: its peers complete normally, and the
+// SIGNAL error word is left alone.
+//
+// hipcc (ROCm 7), gfx950, -O3: VGPRs / AGPRs / SGPRs / scratch bytes per lane
+// / LDS bytes / waves per SIMD
+//     signal_alltoallv_kernel  170 / 0 / 106 / 0 / 1584 / 2
+//     alltoallv_copy_kernel    171 / 0 / 106 / 0 / 1328 / 2
+//     alltoallv_plan_kernel     65 / 0 /  94 / 0 /  800 / 7
+// No scratch memory.  As the collect's, the copy kernel parks 34 SGPRs in VGPR
+// lanes, which its VGPR count includes; the fused kernel none.
+static_assert(kAlltoallvPlanWords <= kBlock, "one block reads the plan");
+
+// one thread; counts, offs and plan are its block's LDS
+__device__ __forceinline__ void alltoallv_exchange(const AlltoallvArgs &c, unsigned long long *counts,
+                                                   unsigned long long *offs, AlltoallvPlan *plan) {
+    if (c.cnt[0]) {
+        unsigned long long x[kMaxFoldInputs], y[kMaxFoldInputs];
+#pragma unroll
+        for (int i = 0; i < kMaxFoldInputs; ++i)
+            if (i < c.P) {
+                x[i] = __hip_atomic_load(c.cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                y[i] = __hip_atomic_load(c.off[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+#pragma unroll
+        for (int i = 0; i < kMaxFoldInputs; ++i)
+            if (i < c.P) {
+                counts[i] = x[i];
+                offs[i] = y[i];
+            }
+    } else {
+        for (int i = 0; i < c.P; ++i) {
+            counts[i] = c.nelems;
+            offs[i] = (unsigned long long)c.m * c.nelems;
+        }
+    }
+    alltoallv_plan(counts, offs, c.P, c.capacity, c.src_capacity, c.esize, c.m, plan);
+    const unsigned long long *w = reinterpret_cast<const unsigned long long *>(plan);
+    for (int k = 0; k < kAlltoallvPlanWords; ++k)
+        __hip_atomic_store(c.plan + k, w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool over = plan->overflow != 0;
+    if (c.where) {
+        for (int i = 0; i < c.P; ++i)
+            __hip_atomic_store(c.where + i, over ? kCollectPoison : plan->offset[i], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(c.where + c.P, over ? kCollectPoison : plan->total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (over)   // this GPU's launches, which never overlap, are the only writer
+        __hip_atomic_store(c.overflows,
+                           __hip_atomic_load(c.overflows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + 1,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// every thread of a block: the plan from the device buffer, then the block's
+// segment list (none on overflow)
+__device__ __forceinline__ void alltoallv_setup(const AlltoallvArgs &c, AlltoallvPlan *plan, const void **srcs,
+                                                CollectSegs *g) {
+    unsigned long long *const w = reinterpret_cast<unsigned long long *>(plan);
+    if (threadIdx.x < kAlltoallvPlanWords)
+        w[threadIdx.x] = __hip_atomic_load(c.plan + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kMaxFoldInputs; ++i) srcs[i] = c.src[i];
+    }
+    __syncthreads();
+    const int nseg = plan->overflow || plan->nseg > (unsigned long long)c.P ? 0 : (int)plan->nseg;
+    const int k = threadIdx.x;
+    if (k < nseg) {
+        const int i = (int)(plan->order[k] % kMaxFoldInputs);
+        const char *s = static_cast<const char *>(srcs[i]) + plan->from[i] * c.esize;
+        char *d = static_cast<char *>(c.tgt) + plan->offset[i] * c.esize;
+        const unsigned long long len = plan->count[i] * c.esize;
+        const bool vec = ((reinterpret_cast<uintptr_t>(s) ^ reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+        unsigned long long head = vec ? (16 - (reinterpret_cast<uintptr_t>(s) & 15)) & 15 : 0;
+        if (head > len) head = len;
+        g->src[k] = s + head;
+        g->dst[k] = d + head;
+        g->len[k] = len;
+        g->head[k] = (unsigned int)head;
+        g->vec[k] = vec ? 1u : 0u;
+        g->units[k] = vec ? (len - head) / 16 : len / c.esize;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long most = 0;
+        for (int j = 0; j < nseg; ++j) most = g->units[j] > most ? g->units[j] : most;
+        g->most = most;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void alltoallv_copy(const AlltoallvArgs &c, const AlltoallvPlan &plan,
+                                               const CollectSegs &g) {
+    const int nseg = plan.overflow || plan.nseg > (unsigned long long)c.P ? 0 : (int)plan.nseg;
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
+    if (c.esize == 4) collect_span<unsigned int>(g, nseg, tid, nthr);
+    else collect_span<unsigned long long>(g, nseg, tid, nthr);
+}
+
+__global__ __launch_bounds__(kBlock) void signal_alltoallv_kernel(SignalAlltoallvArgs a) {
+    __shared__ AlltoallvPlan s_plan;
+    __shared__ unsigned long long s_counts[kMaxFoldInputs], s_offs[kMaxFoldInputs];
+    __shared__ const void *s_srcs[kMaxFoldInputs];
+    __shared__ CollectSegs s_segs;
+    unsigned int gen0;
+    // every source and every table is final; nobody still reads my target
+    fused_entry(a, true, &gen0, [&] { alltoallv_exchange(a.c, s_counts, s_offs, &s_plan); });
+    alltoallv_setup(a.c, &s_plan, s_srcs, &s_segs);
+    alltoallv_copy(a.c, s_plan, s_segs);
+    fused_exit(a);   // nobody reads my source or my tables any more
+}
+
+__global__ __launch_bounds__(64) void alltoallv_plan_kernel(AlltoallvArgs c) {
+    __shared__ AlltoallvPlan s_plan;
+    __shared__ unsigned long long s_counts[kMaxFoldInputs], s_offs[kMaxFoldInputs];
+    if (threadIdx.x == 0) alltoallv_exchange(c, s_counts, s_offs, &s_plan);
+}
+
+__global__ __launch_bounds__(kBlock) void alltoallv_copy_kernel(AlltoallvArgs c) {
+    __shared__ AlltoallvPlan s_plan;
+    __shared__ const void *s_srcs[kMaxFoldInputs];
+    __shared__ CollectSegs s_segs;
+    alltoallv_setup(c, &s_plan, s_srcs, &s_segs);
+    alltoallv_copy(c, s_plan, s_segs);
+}
+
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
 // check counts them); 8-32 blocks measured within 1 us of it
 // (profiles/r05_fused_blocks.txt).
@@ -839,6 +985,48 @@ hipError_t launch_collect_copy(const CollectArgs &c, hipStream_t stream) {
     // the grid from the capacity alone, which every member shares: a lane holds 16 units of a step
     const size_t blocks = (copy_blocks(Span16{0, (size_t)(c.capacity * c.esize / 16), 0}) + 15) / kMaxFoldInputs;
     hipLaunchKernelGGL(collect_copy_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, c);
+    return hipGetLastError();
+}
+
+namespace {
+bool alltoallv_args_ok(const AlltoallvArgs &c) {
+    if (c.P < 1 || c.P > kMaxFoldInputs || c.m < 0 || c.m >= c.P || (c.esize != 4 && c.esize != 8) || !c.tgt ||
+        !c.plan || !c.overflows || c.capacity > SIZE_MAX / c.esize || c.src_capacity > SIZE_MAX / c.esize)
+        return false;
+    if (reinterpret_cast<uintptr_t>(c.tgt) % c.esize || reinterpret_cast<uintptr_t>(c.where) % 8) return false;
+    const bool imm = !c.cnt[0];
+    for (int i = 0; i < c.P; ++i) {
+        if (!c.src[i] || reinterpret_cast<uintptr_t>(c.src[i]) % c.esize) return false;
+        if (imm ? c.cnt[i] || c.off[i] : !c.cnt[i] || !c.off[i]) return false;
+        if ((reinterpret_cast<uintptr_t>(c.cnt[i]) | reinterpret_cast<uintptr_t>(c.off[i])) % 8) return false;
+    }
+    // immediates: every block m * nelems + nelems inside the source
+    if (imm && (c.nelems > c.src_capacity / c.P || c.nelems > c.capacity / c.P)) return false;
+    return true;
+}
+}  // namespace
+
+hipError_t launch_signal_alltoallv(const SignalAlltoallvArgs &a, hipStream_t stream) {
+    if (!a.gsync || !a.sig.seen || !a.sig.fence_stats || a.sig.P < 1 || a.sig.P > kMaxFoldInputs || !a.sig.mine ||
+        !a.sig.err || !alltoallv_args_ok(a.c))
+        return hipErrorInvalidValue;
+    for (int i = 0; i < a.sig.P; ++i)
+        if (a.sig.pe[i] != a.sig.me && !a.sig.peer[i]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(signal_alltoallv_kernel, dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_alltoallv_plan(const AlltoallvArgs &c, hipStream_t stream) {
+    if (!alltoallv_args_ok(c)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(alltoallv_plan_kernel, dim3(1), dim3(64), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_alltoallv_copy(const AlltoallvArgs &c, hipStream_t stream) {
+    if (!alltoallv_args_ok(c)) return hipErrorInvalidValue;
+    // the collect's grid, from the capacity alone, which every member shares: a lane holds 16 units of a step
+    const size_t blocks = (copy_blocks(Span16{0, (size_t)(c.capacity * c.esize / 16), 0}) + 15) / kMaxFoldInputs;
+    hipLaunchKernelGGL(alltoallv_copy_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }
 

@@ -158,6 +158,18 @@ def lib() -> ctypes.CDLL:
     L.shmemx_collect_loopback.argtypes = [i, i, sz, vp, ctypes.POINTER(vp), ullp, sz, i, i, ullp,
                                           ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), vp]
     L.shmemx_collect_loopback.restype = i
+    for bits in (32, 64):
+        getattr(L, f"shmemx_alltoall{bits}_on_stream").argtypes = [vp, vp, sz, i, i, i, vp]
+        getattr(L, f"shmemx_alltoall{bits}_on_stream").restype = i
+        getattr(L, f"shmemx_alltoallv{bits}_on_stream").argtypes = [vp, vp, vp, vp, vp, sz, sz, i, i, i, vp]
+        getattr(L, f"shmemx_alltoallv{bits}_on_stream").restype = i
+    L.shmemx_alltoall_stats.argtypes = [ullp, i, i]
+    L.shmemx_alltoall_stats.restype = i
+    L.shmemx_alltoallv_route.argtypes = [sz, sz, i, ctypes.POINTER(i)]
+    L.shmemx_alltoallv_route.restype = i
+    L.shmemx_alltoallv_loopback.argtypes = [i, i, sz, vp, ctypes.POINTER(vp), ullp, ullp, sz, sz, i, ullp,
+                                            ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_alltoallv_loopback.restype = i
     L.shmemx_set_bcast_twophase_kb.argtypes = [ctypes.c_long]
     L.shmemx_set_bcast_twophase_kb.restype = ctypes.c_long
     L.shmemx_pull_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i, i]
@@ -689,6 +701,73 @@ def collect_loopback(tgt, srcs, counts, capacity: int, esize: int, m: int = 0, f
                                        stream or None)
     _check(rc, f"shmemx_collect_loopback(P={P},m={m},fused={fused},counted={counted}): error word {err.value}")
     return where[0], where[1], over.value, err.value
+
+
+def alltoall_on_stream(bits: int, target, source, nelems: int, PE_start: int, logPE_stride: int, PE_size: int,
+                       stream: int = 0) -> None:
+    """shmemx_alltoall{32,64}_on_stream: heap operands only, PE_size * nelems
+    elements each; my block j goes to member j's block of my index."""
+    rc = getattr(lib(), f"shmemx_alltoall{bits}_on_stream")(addr(target), addr(source), nelems, PE_start,
+                                                            logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_alltoall{bits}_on_stream")
+
+
+def alltoallv_on_stream(bits: int, target, source, send_counts, send_offsets, where_dev, capacity: int,
+                        src_capacity: int, PE_start: int, logPE_stride: int, PE_size: int, stream: int = 0) -> None:
+    """shmemx_alltoallv{32,64}_on_stream: send_counts / send_offsets are
+    8-byte-word heap tables the peers read when the call executes; where_dev
+    (or None) receives the PE_size block offsets and the total received."""
+    rc = getattr(lib(), f"shmemx_alltoallv{bits}_on_stream")(
+        addr(target), addr(source), addr(send_counts), addr(send_offsets), addr(where_dev), capacity, src_capacity,
+        PE_start, logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_alltoallv{bits}_on_stream")
+
+
+ALLTOALL_STATS = ("alltoalls", "alltoallvs", "fused_calls", "overflows")
+
+
+def alltoall_stats(reset: bool = False) -> dict:
+    """shmemx_alltoall_stats: the stream-ordered alltoalls and alltoallvs
+    since the last reset, those of them that ran as one fused launch, and the
+    overflows the device saw (synchronise the stream first)."""
+    buf = (ctypes.c_ulonglong * len(ALLTOALL_STATS))()
+    k = lib().shmemx_alltoall_stats(buf, len(buf), 1 if reset else 0)
+    return {name: buf[i] for i, name in enumerate(ALLTOALL_STATS[:max(0, k)])}
+
+
+def alltoallv_route(esize: int, capacity: int, P: int) -> bool:
+    """shmemx_alltoallv_route: would an alltoallv of this capacity run as one
+    fused launch under the current limit?  Host logic only."""
+    fused = ctypes.c_int(-1)
+    _check(lib().shmemx_alltoallv_route(esize, capacity, P, ctypes.byref(fused)),
+           f"shmemx_alltoallv_route(esize={esize},capacity={capacity},P={P})")
+    return bool(fused.value)
+
+
+def alltoallv_loopback(tgt, srcs, counts, offsets, capacity: int, src_capacity: int, esize: int, m: int = 0,
+                       fused: bool = True, stream: int = 0):
+    """shmemx_alltoallv_loopback: member m's alltoallv launches of a
+    len(srcs)-member set whose arrays are all this process's.  counts and
+    offsets are P x P nested lists, row i what member i sends; both None runs
+    the fixed alltoall of capacity // P elements per pair.  Blocking.  Returns
+    (the P + 1 where words, overflows counted, the device barriers' error
+    word)."""
+    P = len(srcs)
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in srcs])
+    c = o = None
+    if counts is not None or offsets is not None:
+        if counts is None or offsets is None or len(counts) != P or len(offsets) != P or \
+                any(len(r) != P for r in counts) or any(len(r) != P for r in offsets):
+            raise ValueError("counts and offsets are P x P")
+        c = (ctypes.c_ulonglong * (P * P))(*[v for r in counts for v in r])
+        o = (ctypes.c_ulonglong * (P * P))(*[v for r in offsets for v in r])
+    where = (ctypes.c_ulonglong * (P + 1))(*([0] * (P + 1)))
+    over, err = ctypes.c_uint(0), ctypes.c_uint(0)
+    rc = lib().shmemx_alltoallv_loopback(P, m, esize, addr(tgt), a, c, o, capacity, src_capacity,
+                                         1 if fused else 0, where, ctypes.byref(over), ctypes.byref(err),
+                                         stream or None)
+    _check(rc, f"shmemx_alltoallv_loopback(P={P},m={m},fused={fused}): error word {err.value}")
+    return list(where), over.value, err.value
 
 
 PULL_KINDS = {"fcollect": 0, "broadcast": 1}
