@@ -828,6 +828,78 @@ int shmemx_alltoallv_loopback(int P, int m, size_t esize, void *tgt, const void 
                               unsigned int *overflow_out, unsigned int *signal_error,
                               void *stream);
 
+/* Stream-ordered reduce-scatter: the one collective of this family that
+ * folds, under the same device barriers and the same rules as the calls above.
+ * Every member of the set holds a source of PE_size * nelems elements of
+ * `type` and a target of nelems elements.  Element e of the target of the
+ * member with index m in the set receives
+ *   op(...op(op(src_0[m * nelems + e], src_1[m * nelems + e]),
+ *            src_2[m * nelems + e])..., src_{P-1}[m * nelems + e]),
+ * a left fold over the members in SET order, the order
+ * shmemx_fold_n_on_stream documents, for every pair: the result equals
+ * shmemx_fold_n_on_stream on the P blocks bit for bit, long double in soft x87
+ * and the complex products included.  Float, double and long double min and
+ * max take set order too, not the own order of the to_all calls: the
+ * reference has no reduce-scatter, so there is no own-order answer to
+ * reproduce.
+ * When the call completes on the stream the member's target is final and its
+ * source may be overwritten (the exit handshake has seen every peer finish
+ * reading).  shmemx_reduce_scatter_on_stream followed by a kernel of the
+ * caller's own on the slice and shmemx_fcollect{32,64}_on_stream is an
+ * allreduce in one graph with the caller's kernel fused between its halves.
+ *   route       one fused launch while PE_size * nelems * size (the source's
+ *               bytes) is at most the shmemx_set_fused_twoshot_kb limit, else
+ *               five launches: barrier, fold of the P blocks, barrier.
+ *   vectors     the fold runs on 16-byte vectors when the target and all P
+ *               block starts are 16-byte aligned, element by element
+ *               otherwise.  Block m starts m * nelems * size bytes into the
+ *               source, so a caller who wants vectors keeps nelems * size a
+ *               multiple of 16 (and both operands 16-byte aligned).
+ * EINVAL, before any HIP call: a bad set, a pair the reference lacks
+ * (shmemx_op_valid), NULL or not element-aligned target / source with nelems
+ * > 0 (8-byte alignment serves the 16-byte types), PE_size * nelems * size *
+ * 16 wrapping, any overlap of [target, target + nelems * size) with [source,
+ * source + PE_size * nelems * size): there is no in-place form.  EINVAL /
+ * ENOTMEMBER for the set as above.  ENOTSUP, before any launch: an operand
+ * outside the heap, more than 16 members, no intra-node block, a pair with
+ * shmemx_op_on_device == 0.  nelems == 0 launches nothing.  A one-member set
+ * needs no heap: it is one stream-ordered copy.  On the mirrored heap the
+ * host-newer blocks of the source are flushed up and the target's blocks
+ * marked device-newer, as for fcollect.  Calls of one PE share the grid
+ * barrier's words with SIGNAL and the calls above and must not overlap them
+ * in time; capturable after one warm call of the same set. */
+int shmemx_reduce_scatter_on_stream(int type, int op, void *target, const void *source,
+                                    size_t nelems, int PE_start, int logPE_stride,
+                                    int PE_size, void *stream);
+
+/* Pure host logic: *fused = 1 if a stream-ordered reduce-scatter of nelems
+ * elements of `type` per member over P members would run as one fused launch
+ * under the current limit, 0 if unfused or with nothing to launch (nelems ==
+ * 0, P == 1).  EINVAL for an unknown type, P outside 1..16, a wrapping size or
+ * a NULL fused. */
+int shmemx_reduce_scatter_route(int type, size_t nelems, int P, int *fused);
+
+/* Counts of the stream-ordered reduce-scatters since the last reset, up to
+ * nout of them: [0] calls that had work, [1] those that ran as one fused
+ * launch.  shmemx_pull_stats, shmemx_collect_stats and shmemx_alltoall_stats
+ * are unchanged.  Returns how many were written. */
+int shmemx_reduce_scatter_stats(unsigned long long *out, int nout, int reset);
+
+/* Test hook: member m's reduce-scatter launches on one GPU, set up as
+ * shmemx_fused_loopback (the same private signal area, the same 2 s bound,
+ * looped-back handshakes, no shmem_init); waits for them.  srcs[k] is member
+ * k's whole source of P * nelems elements, tgt member m's target.  fused != 0
+ * selects the fused launch, 0 the five unfused launches, whatever the size.
+ * *signal_error as for shmemx_fused_loopback.  Returns OK (at once for nelems
+ * == 0); EDEVICE for a failed launch or a non-zero error word; ENOTSUP for a
+ * pair with no kernel; EINVAL, before any HIP call, for a pair the reference
+ * lacks, P outside 1..16, m outside 0..P-1, a wrapping size or, with nelems >
+ * 0, a NULL or not element-aligned tgt / srcs / entry, or a source that meets
+ * the target. */
+int shmemx_reduce_scatter_loopback(int type, int op, int P, int m, void *tgt,
+                                   const void *const *srcs, size_t nelems, int fused,
+                                   unsigned int *signal_error, void *stream);
+
 /* Largest stream-ordered broadcast, in KiB, that stays one phase (default
  * $SHMEMX_BCAST_TWOPHASE_KB, else 2048: derived, not measured on xGMI; 0 =
  * two phases whenever PE_size > 2).  Every member of a set must hold the same

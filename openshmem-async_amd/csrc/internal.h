@@ -225,6 +225,17 @@ struct SignalPullArgs {
 };
 hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream);
 
+// The stream-ordered reduce-scatter as ONE launch (pull.cpp): the fused two
+// shot above without its second phase.  After the entry handshake every block
+// folds its share of out[i] = op(...op(ins[0][i], ins[1][i])..., ins[nins-1][i])
+// for i < n, where ins[k] is member k's source at this member's block (set
+// order) and out this member's target; then the exit handshake.  No mid
+// handshake, no gather, no tiny path.  lo must be 0 and hi n; two_shot,
+// host_word and the segment list are ignored.  16-byte vectors when out and
+// every ins[k] are 16-byte aligned, else the element loop.  gsync, sig as for
+// launch_signal_fold, whose struct it takes as it stands.
+hipError_t launch_signal_reduce_scatter(int type, int op, const SignalFoldArgs &a, hipStream_t stream);
+
 // The stream-ordered collect (pull.cpp): the members' counts are exchanged on
 // the device.  Member m publishes its count (`count`, or *count_dev read by
 // the call's first kernel; kCollectPoison if it is above `capacity` or

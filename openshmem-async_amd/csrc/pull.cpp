@@ -59,6 +59,15 @@
 //                                      is bad or the total is over capacity
 //              barrier                 nobody reads my source or tables any more
 //              An overflow is the receiver's alone; its peers complete.
+//   reduce-    the one collective here that folds: SIGNAL's two shot without
+//   scatter    its second phase.  Member m's target is the set-
+//              order fold of block m of every member's source:
+//              barrier                 every source is final; nobody reads my target
+//              fold                    block m of all P sources -> my target
+//              barrier                 nobody reads my source any more
+//              One launch (launch_signal_reduce_scatter) while the source's
+//              P * nelems * size bytes are within $SHMEMX_FUSED_TWOSHOT_KB,
+//              above it the unfused barriers around launch_fold_peers.
 // Up to $SHMEMX_FUSED_TWOSHOT_KB (the array for a broadcast, the P-fold target
 // for an fcollect, the target's capacity for a collect or an alltoallv) a call
 // is ONE launch, launch_signal_pull / launch_signal_collect /
@@ -591,6 +600,99 @@ int alltoallv_on_stream(size_t esize, void *target, const void *source, const un
     return SHMEMX_OK;
 }
 
+// ------------------------------------------------------ reduce-scatter
+// shmemx_reduce_scatter_stats: [calls, those that ran as one fused launch]
+enum { kReduceScatters = 0, kReduceScattersFused, kNumReduceScatterStats };
+unsigned long long g_reduce_scatter_stats[kNumReduceScatterStats];
+
+// P * nelems * size * 16 must not wrap
+bool reduce_scatter_size_ok(size_t sz, size_t nelems, int P) {
+    return nelems <= SIZE_MAX / (sz * kMaxFoldInputs) / (size_t)P;
+}
+
+// The source's bytes against the two shot's limit: every member pulls what
+// the two shot's fold phase pulls at that array size.
+bool reduce_scatter_route_fused(size_t sz, size_t nelems, int P) {
+    return (size_t)P * nelems * sz <= fused_twoshot_bytes();
+}
+
+// What an operand must be a multiple of: the element, or 8 bytes for the
+// 16-byte types (two doubles; the x87 slot's 8-byte significand)
+size_t elem_alignment(size_t sz) { return std::min<size_t>(sz, 8); }
+
+// One call's launches.  Fused: one.  Unfused: the two launches of a barrier,
+// the peers fold, the two launches of a barrier: five (signal_reduce's
+// unfused one shot on the P block pointers).
+hipError_t launch_reduce_scatter(int type, int op, const SignalFoldArgs &fa, bool fused, hipStream_t s) {
+    if (fused) return launch_signal_reduce_scatter(type, op, fa, s);
+    hipError_t e = launch_sys_fence(s, fa.sig.seen);   // every source is final; nobody still reads my target
+    if (e == hipSuccess) e = launch_signal(fa.sig, s);
+    if (e == hipSuccess) e = launch_fold_peers(type, op, fa.out, fa.ins, fa.nins, fa.n, s);
+    if (e == hipSuccess) e = launch_sys_fence(s, fa.sig.seen);   // nobody reads my source any more
+    if (e == hipSuccess) e = launch_signal(fa.sig, s);
+    return e;
+}
+
+// Member m's launch arguments: block m of every member's source, set order.
+template <class SrcOf>
+SignalFoldArgs reduce_scatter_args(const SignalArgs &sa, void *tgt, int P, int m, size_t nelems, size_t sz,
+                                   SrcOf src_of) {
+    const void *ins[kMaxFoldInputs];
+    for (int i = 0; i < P; ++i) ins[i] = static_cast<const char *>(src_of(i)) + (size_t)m * nelems * sz;
+    SignalFoldArgs fa = fused_args(sa, tgt, ins, P, nelems);
+    fa.lo = 0;
+    fa.hi = nelems;
+    return fa;
+}
+
+int reduce_scatter_on_stream(int type, int op, void *target, const void *source, size_t nelems, int start,
+                             int logstride, int size, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!set_shape_ok(start, logstride, size) || !op_valid(type, op)) return set_error(SHMEMX_EINVAL);
+    const size_t sz = type_size(type);
+    if (!reduce_scatter_size_ok(sz, nelems, size)) return set_error(SHMEMX_EINVAL);
+    const size_t tbytes = nelems * sz, sbytes = (size_t)size * tbytes;
+    if (tbytes && (!target || !source)) return set_error(SHMEMX_EINVAL);
+    // whole elements: the offsets are symmetric, so this is a shared fact
+    if (tbytes && (!elem_aligned(target, elem_alignment(sz)) || !elem_aligned(source, elem_alignment(sz))))
+        return set_error(SHMEMX_EINVAL);
+    // no in-place form: symmetric offsets again
+    if (tbytes && ranges_meet(target, tbytes, source, sbytes)) return set_error(SHMEMX_EINVAL);
+    Members mb;
+    if (int rc = enter(start, logstride, size, &mb)) return rc;
+    const int P = size, m = mb.m;
+    trace(LOG_REDUCTION, "stream-ordered reduce-scatter: %zu bytes mine, set (%d,%d,%d) member %d", tbytes, start,
+          logstride, size, m);
+    if (!op_on_device(type, op)) return set_error(SHMEMX_ENOTSUP);
+    if (!tbytes) return SHMEMX_OK;
+    if (P == 1) {
+        // no kernel: the one member's source is its whole result
+        hipStream_t s = stream_of(stream);
+        const void *src = heap::device_operand(source, tbytes);
+        heap::DeviceWrite tw(target, tbytes, s);
+        SHMX_HIP(hipMemcpyAsync(tw.ptr(), src, tbytes, hipMemcpyDefault, s));
+        g_reduce_scatter_stats[kReduceScatters] += 1;
+        return SHMEMX_OK;
+    }
+    const bool fused = reduce_scatter_route_fused(sz, nelems, P);
+    uint64_t soff = 0, toff = 0;
+    if (!heap::offset_of(heap::twin(source), sbytes, &soff) || !heap::offset_of(heap::twin(target), tbytes, &toff))
+        return set_error(SHMEMX_ENOTSUP);
+    if (int rc = map_members(&mb)) return rc;
+    hipStream_t s = stream_of(stream);
+    // mirrored heap: the host's stores to the source go to HBM, the target is
+    // DEVICE_NEWER from here
+    (void)heap::device_operand(source, sbytes);
+    heap::DeviceWrite tw(target, tbytes, s);
+    const SignalFoldArgs fa =
+        reduce_scatter_args(mb.sa, mb.hb[m] + toff, P, m, nelems, sz, [&](int i) { return mb.hb[i] + soff; });
+    SHMX_HIP(launch_reduce_scatter(type, op, fa, fused, s));
+    g_reduce_scatter_stats[kReduceScatters] += 1;
+    g_reduce_scatter_stats[kReduceScattersFused] += fused;
+    return SHMEMX_OK;
+}
+
 }  // namespace
 
 }  // namespace shmx
@@ -598,6 +700,58 @@ int alltoallv_on_stream(size_t esize, void *target, const void *source, const un
 using namespace shmx;
 
 extern "C" {
+
+int shmemx_reduce_scatter_on_stream(int type, int op, void *target, const void *source, size_t nelems,
+                                    int PE_start, int logPE_stride, int PE_size, void *stream) {
+    return reduce_scatter_on_stream(type, op, target, source, nelems, PE_start, logPE_stride, PE_size, stream);
+}
+
+int shmemx_reduce_scatter_route(int type, size_t nelems, int P, int *fused) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    const size_t sz = type_size(type);
+    if (!fused || !sz || P < 1 || P > kMaxFoldInputs || !reduce_scatter_size_ok(sz, nelems, P))
+        return set_error(SHMEMX_EINVAL);
+    *fused = nelems && P > 1 && reduce_scatter_route_fused(sz, nelems, P) ? 1 : 0;
+    return SHMEMX_OK;
+}
+
+int shmemx_reduce_scatter_stats(unsigned long long *out, int nout, int reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    const int k = std::max(0, std::min(nout, (int)kNumReduceScatterStats));
+    for (int i = 0; out && i < k; ++i) out[i] = g_reduce_scatter_stats[i];
+    if (reset)
+        for (unsigned long long &v : g_reduce_scatter_stats) v = 0;
+    return out ? k : 0;
+}
+
+int shmemx_reduce_scatter_loopback(int type, int op, int P, int m, void *tgt, const void *const *srcs,
+                                   size_t nelems, int fused, unsigned int *signal_error_out, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    clear_error();
+    if (!op_valid(type, op) || P < 1 || P > kMaxFoldInputs || m < 0 || m >= P) return set_error(SHMEMX_EINVAL);
+    const size_t sz = type_size(type);
+    if (!reduce_scatter_size_ok(sz, nelems, P)) return set_error(SHMEMX_EINVAL);
+    if (!op_on_device(type, op)) return set_error(SHMEMX_ENOTSUP);
+    if (nelems == 0) return SHMEMX_OK;
+    if (!tgt || !srcs || !elem_aligned(tgt, elem_alignment(sz))) return set_error(SHMEMX_EINVAL);
+    for (int i = 0; i < P; ++i)
+        if (!srcs[i] || !elem_aligned(srcs[i], elem_alignment(sz)) ||
+            ranges_meet(tgt, nelems * sz, srcs[i], (size_t)P * nelems * sz))
+            return set_error(SHMEMX_EINVAL);
+    const LocalDevice dev(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SignalArgs sa{};
+    if (!loopback_signal_args(P, &sa)) return set_error(SHMEMX_ENOMEM);
+    const SignalFoldArgs fa = reduce_scatter_args(sa, tgt, P, m, nelems, sz, [&](int i) { return srcs[i]; });
+    hipError_t e = launch_reduce_scatter(type, op, fa, fused != 0, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const unsigned int err = signal_error();
+    if (signal_error_out) *signal_error_out = err;
+    if (e != hipSuccess || err) return set_error(SHMEMX_EDEVICE);
+    return SHMEMX_OK;
+}
 
 int shmemx_barrier_on_stream(int PE_start, int logPE_stride, int PE_size, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);

@@ -868,6 +868,40 @@ __global__ __launch_bounds__(kBlock) void alltoallv_copy_kernel(AlltoallvArgs c)
     alltoallv_copy(c, s_plan, s_segs);
 }
 
+// ------------------------------------------------ reduce-scatter (SIGNAL)
+// The stream-ordered reduce-scatter (pull.cpp): the fused two shot's first
+// phase alone.  After the entry handshake (every source is final; nobody still
+// reads my target) every block folds its share of the P blocks ins[k] (member
+// k's source at this member's block, set order) into out, elements [lo, hi) =
+// [0, nelems); the exit handshake tells the peers that this member reads their
+// sources no more.  No mid handshake and no gather: nobody reads a target.
+// No tiny path and no host word: the call never blocks.
+//
+// The fold is fold_span under its rule: 16-byte vectors when the target and
+// all P block starts are 16-byte aligned, the element loop otherwise; no
+// realigned vectors.
+//
+// hipcc (ROCm 7), gfx950, -O3, per instance: VGPRs / AGPRs / SGPRs / scratch
+// bytes per lane / waves per SIMD
+//     int          sum    110 / 0 / 84 /  0 / 4
+//     double       sum    110 / 0 / 84 /  0 / 4
+//     float        min    110 / 0 / 80 /  0 / 4
+//     long double  sum     40 / 0 / 98 / 40 / 8
+//     complexd     prod    40 / 0 / 56 /  0 / 8
+// Every light instance (every pair but soft x87's and the complex products)
+// has 110-113 VGPRs, 80-84 SGPRs, 4 waves per SIMD and no scratch memory, and
+// no instance spills a register.  Of the heavy ones only long double sum and
+// product use scratch, the 40 bytes per lane of soft x87's rounding that
+// signal_fold2_kernel<ld80, sum> has too: it is the same fold.
+template <typename T, int OP>
+__global__ __launch_bounds__(kBlock) void signal_reduce_scatter_kernel(SignalFoldArgs a) {
+    unsigned int gen0;
+    fused_entry(a, true, &gen0);        // every source is final; nobody still reads my target
+    const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x, nthr = (size_t)gridDim.x * kBlock;
+    fold_span<T, OP>(a, tid, nthr);     // my block of every member's source
+    fused_exit(a);                      // nobody reads my source any more
+}
+
 // Blocks of the fused launches: kFenceBlocks, so every XCD gets 8 (the entry
 // check counts them); 8-32 blocks measured within 1 us of it
 // (profiles/r05_fused_blocks.txt).
@@ -942,6 +976,24 @@ hipError_t launch_signal_pull(const SignalPullArgs &a, hipStream_t stream) {
     }
     hipLaunchKernelGGL(signal_pull_kernel, dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
+}
+
+hipError_t launch_signal_reduce_scatter(int type, int op, const SignalFoldArgs &a, hipStream_t stream) {
+    if (!op_on_device(type, op) || a.nins < 1 || a.nins > kMaxFoldInputs || !a.out || !a.gsync ||
+        !a.sig.seen || !a.sig.fence_stats || a.sig.P < 1 || a.sig.P > kMaxFoldInputs || !a.sig.mine ||
+        !a.sig.err || a.lo != 0 || a.hi != a.n)
+        return hipErrorInvalidValue;
+    for (int k = 0; k < a.nins; ++k)
+        if (!a.ins[k]) return hipErrorInvalidValue;
+    for (int i = 0; i < a.sig.P; ++i)
+        if (a.sig.pe[i] != a.sig.me && !a.sig.peer[i]) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    with_type_op(type, op, [&](auto t, auto o) {
+        hipLaunchKernelGGL((signal_reduce_scatter_kernel<typename decltype(t)::type, decltype(o)::value>),
+                           dim3(kFusedBlocks), dim3(kBlock), 0, stream, a);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 namespace {

@@ -170,6 +170,15 @@ def lib() -> ctypes.CDLL:
     L.shmemx_alltoallv_loopback.argtypes = [i, i, sz, vp, ctypes.POINTER(vp), ullp, ullp, sz, sz, i, ullp,
                                             ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), vp]
     L.shmemx_alltoallv_loopback.restype = i
+    L.shmemx_reduce_scatter_on_stream.argtypes = [i, i, vp, vp, sz, i, i, i, vp]
+    L.shmemx_reduce_scatter_on_stream.restype = i
+    L.shmemx_reduce_scatter_route.argtypes = [i, sz, i, ctypes.POINTER(i)]
+    L.shmemx_reduce_scatter_route.restype = i
+    L.shmemx_reduce_scatter_stats.argtypes = [ullp, i, i]
+    L.shmemx_reduce_scatter_stats.restype = i
+    L.shmemx_reduce_scatter_loopback.argtypes = [i, i, i, i, vp, ctypes.POINTER(vp), sz, i,
+                                                 ctypes.POINTER(ctypes.c_uint), vp]
+    L.shmemx_reduce_scatter_loopback.restype = i
     L.shmemx_set_bcast_twophase_kb.argtypes = [ctypes.c_long]
     L.shmemx_set_bcast_twophase_kb.restype = ctypes.c_long
     L.shmemx_pull_stats.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), i, i]
@@ -770,7 +779,54 @@ def alltoallv_loopback(tgt, srcs, counts, offsets, capacity: int, src_capacity: 
     return list(where), over.value, err.value
 
 
-PULL_KINDS = {"fcollect": 0, "broadcast": 1}
+def reduce_scatter_on_stream(type_name: str, op: str, target, source, nelems: int, PE_start: int,
+                             logPE_stride: int, PE_size: int, stream: int = 0) -> None:
+    """shmemx_reduce_scatter_on_stream: heap operands only; the source holds
+    PE_size * nelems elements, the target nelems: the set-order fold of this
+    member's block of every member's source."""
+    rc = lib().shmemx_reduce_scatter_on_stream(TYPES[type_name], OPS[op], addr(target), addr(source), nelems,
+                                               PE_start, logPE_stride, PE_size, stream or None)
+    _check(rc, f"shmemx_reduce_scatter_on_stream({type_name},{op})")
+
+
+def reduce_scatter_route(type_name: str, nelems: int, P: int) -> bool:
+    """shmemx_reduce_scatter_route: would a reduce-scatter of nelems elements
+    per member run as one fused launch under the current limit?  Host logic
+    only."""
+    fused = ctypes.c_int(-1)
+    _check(lib().shmemx_reduce_scatter_route(TYPES[type_name], nelems, P, ctypes.byref(fused)),
+           f"shmemx_reduce_scatter_route({type_name},nelems={nelems},P={P})")
+    return bool(fused.value)
+
+
+REDUCE_SCATTER_STATS = ("calls", "fused_calls")
+
+
+def reduce_scatter_stats(reset: bool = False) -> dict:
+    """shmemx_reduce_scatter_stats: the stream-ordered reduce-scatters since
+    the last reset and those that ran as one fused launch."""
+    buf = (ctypes.c_ulonglong * len(REDUCE_SCATTER_STATS))()
+    k = lib().shmemx_reduce_scatter_stats(buf, len(buf), 1 if reset else 0)
+    return {name: buf[i] for i, name in enumerate(REDUCE_SCATTER_STATS[:max(0, k)])}
+
+
+def reduce_scatter_loopback(type_name: str, op: str, tgt, srcs, nelems: int, m: int = 0, fused: bool = True,
+                            stream: int = 0) -> int:
+    """shmemx_reduce_scatter_loopback: member m's reduce-scatter launches of a
+    len(srcs)-member set whose arrays (each source len(srcs) * nelems
+    elements) are all this process's, the handshakes looped back.  Blocking.
+    Returns the device barriers' error word (0 when the call returned OK)."""
+    P = len(srcs)
+    a = (ctypes.c_void_p * P)(*[addr(x) for x in srcs])
+    err = ctypes.c_uint(0)
+    rc = lib().shmemx_reduce_scatter_loopback(TYPES[type_name], OPS[op], P, m, addr(tgt), a, nelems,
+                                              1 if fused else 0, ctypes.byref(err), stream or None)
+    _check(rc, f"shmemx_reduce_scatter_loopback({type_name},{op},P={P},m={m},fused={fused}): "
+               f"error word {err.value}")
+    return err.value
+
+
+PULL_KINDS ={"fcollect": 0, "broadcast": 1}
 
 
 @dataclass
